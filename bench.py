@@ -9,9 +9,12 @@ its own 16384-instance shard, there is no collective in the data path
 (exit_mode='fixed' takes no batch-global decision).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run times only the headline solve; --full adds the
+sub-records (the other dtype, newton_step, ipm) and the CPU oracle baseline to that line.
+--dump-outputs DIR writes what the last timed step returned (rank 0's shard) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -95,8 +98,12 @@ def main():
     ap.add_argument("--nx", type=int, default=13)
     ap.add_argument("--nu", type=int, default=4)
     ap.add_argument("--al-iter", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the f64 / newton_step / ipm sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the f64 / newton_step / ipm sub-records and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the f64 / newton_step / ipm sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--variant", default="auto", choices=["auto", "team", "quad"])
     args = ap.parse_args()
 
@@ -163,10 +170,15 @@ def main():
 
         elapsed, kernel_ms = timed(torch, step, steps, warmup, barrier)
         ok = bool((info == 0).all().item()) and bool((status == 1).all().item())
-        return elapsed, kernel_ms, ok, p
+        last = total - 1
+        outputs = {"z": zs[last], "lam": lams[last], "rho": rhos[last], "phi": phi, "rnorm2": rn2,
+                   "info": info, "status": status}
+        return elapsed, kernel_ms, ok, p, outputs
 
-    elapsed, kernel_ms, ok, p = run_solve(args.dtype, args.steps, args.warmup)
+    elapsed, kernel_ms, ok, p, outputs = run_solve(args.dtype, args.steps, args.warmup)
     variant = be.last_variant  # what 'auto' resolved to (quad from B = 4096 per GPU, team below)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs, torch.float32 if args.dtype == "f32" else torch.float64)
 
     if world > 1:
         tmax = torch.tensor([elapsed, 0.0 if ok else 1.0], dtype=torch.float64,
@@ -176,7 +188,7 @@ def main():
         ok = float(tmax[1].item()) == 0.0
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         extras = bench_extras(args, torch, be, _lib, dev, dims, p, run_solve, barrier)
 
     if rank == 0:
@@ -225,11 +237,31 @@ def main():
                                  "traffic, not by the algorithmic bytes (DESIGN.md section 5)"},
         }
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, T, nx, nu)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 63_000_000   # data bytes of one --dump-outputs set; the .npy headers stay within 64 MB with it
+
+
+def dump_outputs(path, outputs, dtype):
+    """The arrays the timed call returns (batch-first), each as path/<name>.npy in `dtype` (info and status
+    converted). Above DUMP_BYTES the same seeded sample of instances is taken from every array."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(outputs.values())).shape[0]
+    per_instance = sum(a[0].numel() for a in outputs.values()) * dtype.itemsize
+    idx = None
+    if per_instance * B > DUMP_BYTES:
+        k = DUMP_BYTES // per_instance
+        idx = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+    for name, a in outputs.items():
+        a = a.detach().to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a[idx])
 
 
 def bench_extras(args, torch, be, _lib, dev, dims, p, run_solve, barrier):
@@ -241,7 +273,7 @@ def bench_extras(args, torch, be, _lib, dev, dims, p, run_solve, barrier):
     out = {}
     other = "f64" if args.dtype == "f32" else "f32"
     try:
-        el, kms, ok2, _ = run_solve(other, max(3, args.steps // 4), 2)
+        el, kms, ok2, _, _ = run_solve(other, max(3, args.steps // 4), 2)
         steps2 = max(3, args.steps // 4)
         sz = 8 if other == "f64" else 4
         out[other] = {"value": B * steps2 / el, "unit": "QP solves/s", "ms_per_step": 1e3 * el / steps2,

@@ -36,7 +36,7 @@ def test_restatement_jacobian_is_the_derivative_of_the_step():
     assert np.abs(num - B[:, :, 0]).max() < 1e-7
 
 
-@pytest.mark.skipif(not dyn_py.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
+@pytest.mark.skipif(not dyn_py.have_ref(), reason="oracle/_ref not built (the reference sources were not available to build())")
 def test_compiled_reference_reproduces_its_fixture():
     xn, A, B = dyn_py.pendulum1l_ref(GOLD["x"][:32], GOLD["u"][:32], 0.05)
     assert np.array_equal(xn, GOLD["h05_xn"][:32]) and np.array_equal(A, GOLD["h05_A"][:32])

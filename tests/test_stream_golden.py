@@ -187,8 +187,8 @@ def test_linearize_once_outside_stream_raises_like_the_reference():
 # ---- the adapter: policies.Tracking_MPC's call sequence, restated in a few lines -----------------
 class _TrackingAdapter:
     """What the reference's Tracking_MPC does around the solver (policies.py:1236-1310), so that the
-    recorded traces can be replayed where /root/reference is absent (the GPU box). The unchanged
-    reference class itself drives our solver in tests/test_dropin_reference_policies.py."""
+    recorded traces can be replayed without the reference. The traces were recorded from the unchanged
+    reference class (tools/gen_golden.py, tools/gen_golden_stream.py)."""
 
     def __init__(self, ctrl, B, T, nx, nu, dt, dev):
         self.ctrl, self.x_init, self.u_init = ctrl, None, None

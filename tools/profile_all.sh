@@ -5,9 +5,9 @@ set -uo pipefail
 OUT=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/trace.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_$c" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/pmc_$c.log" 2>&1 || echo "pmc pass $c failed"
+  rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_$c" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/pmc_$c.log" 2>&1 || echo "pmc pass $c failed"
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys, collections
