@@ -474,7 +474,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 if (tr.d && active) {
                     real *td = tr.d + ((size_t)step_id * a.B + b) * T * N;
                     for (int t = 0; t < T; ++t)
-                        for (int j = qd.q; j < N; j += 4) td[t * N + j] = qd.recp(t)[C::oY + C::pn(j)];
+                        for (int j = qd.q; j < N; j += 4) td[t * N + j] = qd.recp(t)[C::wn(C::oY, j)];
                 }
             }
             if constexpr (NL) qd.template merit_nonlin<Dyn>(ph);
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         real *Qg = a.Qd_grad + (size_t)b * T * N;
         for (int t = 0; t < T; ++t)
             for (int j = qd.q; j < N; j += 4) {
-                const real w = qd.recp(t)[C::oY + C::pn(j)];
+                const real w = qd.recp(t)[C::wn(C::oY, j)];
                 qg[t * N + j] = w;
                 Qg[t * N + j] = w * zf[t * N + j];
             }

@@ -33,6 +33,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "alqp_team.hpp"  // fma_, rsqrt_, fmax_, fabs_, pad4
 #include "alqp_dyn.hpp"   // inlinable dynamics models (nonlinear fused solve)
 
@@ -168,6 +170,28 @@ struct NoDyn {
     static constexpr int ID = 0;
 };
 
+// a vector field of a workspace record (QCfg): word offsets of its head and its tail; `record pointer + field` names
+// the field of that record for the ld_* / st_* accessors of Quad
+struct Fld {
+    int h, t;
+};
+// the fields of QCfg carry their offsets in the type (a static constexpr object of class type is read from memory at
+// run time in device code)
+template <int H, int T>
+struct FldT {
+    static constexpr int h = H, t = T;
+    __host__ __device__ constexpr operator Fld() const { return {H, T}; }
+};
+template <typename real>
+struct FRef {
+    real *p;
+    Fld f;
+};
+template <typename real, int H, int T>
+__device__ __forceinline__ FRef<std::remove_const_t<real>> operator+(real *p, FldT<H, T>) {
+    return {const_cast<std::remove_const_t<real> *>(p), Fld{H, T}};
+}
+
 template <typename real, int NX_, int NU_>
 struct QCfg {
     static constexpr int NX = NX_, NU = NU_, N = NX_ + NU_;
@@ -177,14 +201,30 @@ struct QCfg {
     static constexpr int HT = 2 * SH * (SH + 1);  // registers of the trimmed H panel: slot s has 4(s+1) columns
     __host__ __device__ static constexpr int hidx(int s, int j) { return 2 * s * (s + 1) + j; }
     static constexpr int ST = 2 * SW * (SW + 1);  // same trimming for the Schur accumulator
-    // workspace record of one (instance, stage), in reals. L: slot s is s+1 chunks of 4 words
-    // per lane, the lanes of a quad interleaved (64 contiguous bytes per chunk); in the last
-    // slot only the NLAST lanes that own a real row store anything.
+    // ---- record layout. Words are placed in 16-word groups (64 bytes in fp32): every per-lane access of a sweep is
+    // one 4-word chunk of a group, or single words of one group, at the group's start + a lane offset.
+    // Wave-interleaved records (fp32, IL = 2): the records of instances 2i and 2i+1 at the same stage alternate in
+    // 64-byte blocks (group g of instance 2i + h at word 32 g + 16 h of the pair's 2 RECW words), so the quad of one
+    // instance and the quad of its partner fill whole 128-byte lines with one memory instruction where the
+    // per-instance layout touched 16 half lines. fp64 (IL = 1) keeps one record after the other: a quad's 4 x 32
+    // bytes already fill a line.
+    static constexpr int BLK = 64 / (int)sizeof(real);      // reals of a 64-byte block
+#ifndef ALQP_REC_IL_F32
+#define ALQP_REC_IL_F32 2
+#endif
+    static constexpr int IL = sizeof(real) == 4 ? ALQP_REC_IL_F32 : 1;     // instances interleaved
+    static_assert(IL == 1 || BLK == 16, "groups of 16 words are 64-byte blocks");
+    // logical record word x -> word offset from the instance's record start (rec_base + t * RSTR)
+    __host__ __device__ static constexpr int w(int x) { return (x / 16) * (16 * IL) + x % 16; }
+    // L: slot s is s+1 chunks of 4 words per lane, the lanes of a quad interleaved (64 contiguous bytes per chunk);
+    // in the last slot only the NLAST lanes that own a real row store anything (3 lanes: chunk stride 16, so
+    // that no chunk crosses a group)
     static constexpr int NLAST = N - 4 * (SH - 1);                       // valid rows of the last slot (1..4)
     __host__ __device__ static constexpr int lanes_of(int s) { return s == SH - 1 ? NLAST : 4; }
+    __host__ __device__ static constexpr int lstride(int s) { return lanes_of(s) == 3 ? 16 : 4 * lanes_of(s); }
     __host__ __device__ static constexpr int lbase(int s) {             // word offset of slot s
         int o = 0;
-        for (int i = 0; i < s; ++i) o += (i + 1) * 4 * lanes_of(i);
+        for (int i = 0; i < s; ++i) o += (i + 1) * lstride(i);
         return o;
     }
     static constexpr int LW = lbase(SH);
@@ -205,33 +245,76 @@ struct QCfg {
     // of z and lam, copies of diag Q, q, c and the bounds): in their own arrays these are 52-68
     // byte pieces, each costing one or two 128-byte lines per touch; side by side in the record
     // the sweeps and the line search touch a few whole lines. stage_in()/stage_out() copy them.
-    static constexpr int oL = 0;
-    static constexpr int oY = oL + p4(LW);         // y_t, later d_t : element k at oY + k
-    static constexpr int oR = oY + 4 * SY;         // r_t (eq residual of row block t): row r at oR + r
-    static constexpr int oS = oR + 4 * SW;         // s_t = (J d)_eq
-    static constexpr int oZ = oS + 4 * SW;         // z_t
-    static constexpr int oLE = oZ + 4 * SY;        // lam, equality row block t
-    // the bound rows of stage t, lane-major like the vectors: words 4q..4q+3 = (lam_upper, lam_lower, u_upper,
-    // u_lower) of the ONE control lane q owns (element NX + ju with (NX + ju) % 4 == q; zeros when it owns none)
+    //
+    // Vector fields, lane-major: a field of S own slots per lane (S = SY for an n-vector, SW for an nx-vector, 4 for
+    // the bound rows) is 4 S words. Slot m of lane q: for m < 4 (S / 4) in the HEAD, word 16 (m / 4) + 4 q + m % 4
+    // (whole 16-word chunks, group-aligned: one 16-byte access per lane and chunk); the other S % 4 slots in the TAIL:
+    // word t + 4 q + m - 4 (S / 4) of a tail group, where the tails of several fields share a group (field offsets t
+    // within a lane's 4 words). Head and tail words of a lane are then the same lane offset (16 q bytes) from the
+    // record's address: one address register pair per record. Padding words hold zeros.
+    // Fields: y/d, z, r, s, lam (equality row block t), bound rows, diag Q, q, c. The heads of y and z come first, in
+    // front of L: the sweeps read them from the NEXT stage's record too, and at the start of a record those reads stay
+    // within the 4 KB immediate offset of the current stage's address (no second address register pair).
+    static constexpr int NF = 9;
+    __host__ __device__ static constexpr int fslots(int i) { return (i <= 1 || i == 6 || i == 7) ? SY : (i == 5 ? 4 : SW); }
+    static constexpr int oL = 2 * 16 * (SY / 4);
+    // the tail groups behind L (a field's tail slots never split over two groups); then the other heads
+    __host__ __device__ static constexpr int tail_at(int i) {   // group start + the field's word within a lane's 4
+        int g = (oL + LW + 15) & ~15, o = 0;
+        for (int k = 0; k < NF; ++k) {
+            const int r = fslots(k) % 4;
+            if (r > 0 && o + r > 4) { g += 16; o = 0; }
+            if (k == i) return g + o;
+            o += r;
+        }
+        return o > 0 ? g + 16 : g;   // i == NF: end of the tail groups
+    }
+    __host__ __device__ static constexpr int head_at(int i) {
+        if (i < 2) return i * 16 * (SY / 4);
+        int o = tail_at(NF);
+        for (int k = 2; k < i; ++k) o += 16 * (fslots(k) / 4);
+        return o;
+    }
+    static constexpr FldT<head_at(0), tail_at(0)> oY{};    // y_t, later d_t (n)
+    static constexpr FldT<head_at(1), tail_at(1)> oZ{};    // z_t (n)
+    static constexpr FldT<head_at(2), tail_at(2)> oR{};    // r_t, eq residual of row block t (nx)
+    static constexpr FldT<head_at(3), tail_at(3)> oS{};    // s_t = (J d)_eq (nx)
+    static constexpr FldT<head_at(4), tail_at(4)> oLE{};   // lam, equality row block t (nx)
+    // the bound rows of stage t: lane q's chunk = (lam_upper, lam_lower, u_upper, u_lower) of the ONE control lane q
+    // owns (element NX + ju with (NX + ju) % 4 == q; zeros when it owns none)
     static_assert(NU <= 4, "the u-slot layout holds one control per lane");
-    static constexpr int oUS = oLE + 4 * SW;
-    static constexpr int oQ = oUS + 16;            // diag Q_t
-    static constexpr int oq = oQ + 4 * SY;         // q_t
-    static constexpr int oC = oq + 4 * SY;         // c_t
-    static constexpr int RECW = (oC + 4 * SW + 31) & ~31;  // whole 128-byte lines (fp32)
-    // lane-major placement inside a vector field: element k of an n-vector (fields oY, oZ, oQ, oq; 4*SY words),
-    // row r of an nx-vector (fields oR, oS, oLE, oC; 4*SW words). Padding words hold zeros.
-    __host__ __device__ static constexpr int pn(int k) { return (k & 3) * SY + (k >> 2); }
-    __host__ __device__ static constexpr int px(int r) { return (r & 3) * SW + (r >> 2); }
+    static constexpr FldT<head_at(5), tail_at(5)> oUS{};
+    static constexpr FldT<head_at(6), tail_at(6)> oQ{};    // diag Q_t (n)
+    static constexpr FldT<head_at(7), tail_at(7)> oq{};    // q_t (n)
+    static constexpr FldT<head_at(8), tail_at(8)> oC{};    // c_t (nx)
+    static constexpr int RECW = (head_at(NF) + 31) & ~31;  // whole 128-byte lines (fp32)
+    static_assert(IL == 1 || RECW % 16 == 0, "whole groups per record");
+    // position of slot m of lane q in a field read whole (ld_rep_*: head words, then tail words)
+    template <int S>
+    __host__ __device__ static constexpr int lp(int m, int q) {
+        return m < 4 * (S / 4) ? 16 * (m / 4) + 4 * q + m % 4 : 16 * (S / 4) + q * (S % 4) + m - 4 * (S / 4);
+    }
+    // record word of position p of a field read whole (lp)
+    template <int S>
+    __host__ __device__ static constexpr int fw(Fld f, int p) {
+        return p < 16 * (S / 4) ? w(f.h + p) : w(f.t + 4 * ((p - 16 * (S / 4)) / (S % 4)) + (p - 16 * (S / 4)) % (S % 4));
+    }
+    // element k of an n-vector field (k = 4m + q), row r of an nx-vector field
+    __host__ __device__ static constexpr int pn(int k) { return lp<SY>(k >> 2, k & 3); }
+    __host__ __device__ static constexpr int px(int r) { return lp<SW>(r >> 2, r & 3); }
+    // word offset (from the record start, interleave included) of element k of n-vector field f
+    __host__ __device__ static constexpr int wn(Fld f, int k) { return fw<SY>(f, pn(k)); }
     __host__ __device__ static constexpr int M(int T) { return T * NX + 2 * T * NU; }
     // ONE mapping from (instance, stage) to the workspace: every kernel addresses its records through rec_base()
-    // (+ t * RECW + word), and the size the caller allocates is checked on the host against the highest word that
-    // mapping can touch (ws_covers) - so a future layout (e.g. blocks of 16 interleaved instances, where the padding
-    // quads of a batch that is not a multiple of 16 have records of their own) cannot silently outgrow ws_words().
-    __host__ __device__ static constexpr size_t rec_base(int b, int T) { return (size_t)b * T * RECW; }
-    __host__ __device__ static constexpr size_t ws_words(int B, int T) { return (size_t)B * T * RECW; }
-    // padding quads alias instance B - 1 (k_*_quad: `b = active ? b_raw : B - 1`), so b never exceeds B - 1
-    __host__ static bool ws_covers(int B, int T) { return rec_base(B - 1, T) + (size_t)(T - 1) * RECW + RECW <= ws_words(B, T); }
+    // (+ t * RSTR + w(word)), and the size the caller allocates is checked on the host against the highest word that
+    // mapping can touch (ws_covers). Padding quads alias instance B - 1 (k_*_quad: `b = active ? b_raw : B - 1`); with
+    // an odd B the last pair's second half is allocated and never touched.
+    static constexpr int RSTR = RECW * IL;   // words from stage t to stage t + 1 of one instance
+    __host__ __device__ static constexpr size_t rec_base(int b, int T) { return (size_t)(b / IL) * T * RSTR + (size_t)(b % IL) * 16; }
+    __host__ __device__ static constexpr size_t ws_words(int B, int T) { return (size_t)((B + IL - 1) / IL) * T * RSTR; }
+    __host__ static bool ws_covers(int B, int T) {
+        return rec_base(B - 1, T) + (size_t)(T - 1) * RSTR + w(RECW - 1) + 1 <= ws_words(B, T);
+    }
 };
 
 template <typename real, int NX, int NU>
@@ -263,7 +346,7 @@ struct Quad {
 
     __device__ __forceinline__ real uhi(int t, int j) const { return guhi[t * st_u + j]; }
     __device__ __forceinline__ real ulo(int t, int j) const { return gulo[t * st_u + j]; }
-    __device__ __forceinline__ real *recp(int t) const { return rec + (size_t)t * RECW; }
+    __device__ __forceinline__ real *recp(int t) const { return rec + (size_t)t * C::RSTR; }
 #ifdef ALQP_PHASE_TIMING
     // debug build only (tools/phase_timing.py): cycles per phase; a stamp drains the memory queue,
     // so "wait" buckets hold the exposed latency of the loads issued before them
@@ -281,13 +364,52 @@ struct Quad {
 #define ALQP_STAMP(b)
 #endif
 
-    // ---- lane-major vector fields of a record (QCfg::pn / px) ----
+    // ---- lane-major vector fields of a record (QCfg: head chunks and tail; QCfg::pn / px) ----
+    // own slots m < L of a field of S slots per lane: one 16-byte access per head chunk, single words in the tail
+    template <int S, int L>
+    __device__ __forceinline__ void ld_slots(FRef<real> f, real (&v)[L]) const {
+        static_assert(L <= S, "slots of the field");
+#pragma unroll
+        for (int c = 0; 4 * c < L && c < S / 4; ++c) {
+            const real *p = f.p + C::w(f.f.h + 16 * c) + 4 * q;
+            if (4 * c + 3 < L) gld4(p, v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
+            else
+#pragma unroll
+                for (int i = 0; 4 * c + i < L; ++i) v[4 * c + i] = p[i];
+        }
+        constexpr int H = 4 * (S / 4), R = S % 4;
+        if constexpr (L > H) {
+            const real *p = f.p + C::w(f.f.t) + 4 * q;
+#pragma unroll
+            for (int m = H; m < L; ++m) v[m] = p[m - H];
+        }
+    }
+    template <int S>
+    __device__ __forceinline__ void st_slots(FRef<real> f, const real (&v)[S]) const {
+#pragma unroll
+        for (int c = 0; c < S / 4; ++c) gst4(f.p + C::w(f.f.h + 16 * c) + 4 * q, v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
+        constexpr int H = 4 * (S / 4), R = S % 4;
+        if constexpr (R > 0) {
+            real *p = f.p + C::w(f.f.t) + 4 * q;
+#pragma unroll
+            for (int m = H; m < S; ++m) p[m - H] = v[m];
+        }
+    }
+    // the whole field (4 S words) into w[], positions QCfg::lp
+    template <int S>
+    __device__ __forceinline__ void ld_field(FRef<real> f, real (&w)[4 * S]) const {
+        constexpr int H = 16 * (S / 4), R = S % 4;
+#pragma unroll
+        for (int c = 0; c < H; c += 4) gld4(f.p + C::w(f.f.h + c), w[c], w[c + 1], w[c + 2], w[c + 3]);
+#pragma unroll
+        for (int i = H; i < H + 4 * R; ++i) w[i] = f.p[C::template fw<S>(f.f, i)];
+    }
     // own elements: k = 4m + q (m < SY) of an n-vector, rows r = 4s + q (s < SW) of an nx-vector;
     // slots without an element read / write the field's zero padding
-    __device__ __forceinline__ void ld_own_n(const real *field, real (&v)[SY]) const { gload<SY>(field + q * SY, v); }
-    __device__ __forceinline__ void ld_own_x(const real *field, real (&v)[SW]) const { gload<SW>(field + q * SW, v); }
+    __device__ __forceinline__ void ld_own_n(FRef<real> f, real (&v)[SY]) const { ld_slots<SY, SY>(f, v); }
+    __device__ __forceinline__ void ld_own_x(FRef<real> f, real (&v)[SW]) const { ld_slots<SW, SW>(f, v); }
     // x-part rows 4s + q of an n-vector (rows >= NX: whatever element 4s+q holds, finite)
-    __device__ __forceinline__ void ld_ownx_of_n(const real *field, real (&v)[SW]) const { gload<SW>(field + q * SY, v); }
+    __device__ __forceinline__ void ld_ownx_of_n(FRef<real> f, real (&v)[SW]) const { ld_slots<SY, SW>(f, v); }
     template <int LEN>
     __device__ __forceinline__ void gstore(real *p, const real (&v)[LEN]) const {
 #pragma unroll
@@ -295,26 +417,30 @@ struct Quad {
 #pragma unroll
         for (int c = (LEN / 4) * 4; c < LEN; ++c) p[c] = v[c];
     }
-    __device__ __forceinline__ void st_own_n(real *field, const real (&v)[SY]) const { gstore<SY>(field + q * SY, v); }
-    __device__ __forceinline__ void st_own_x(real *field, const real (&v)[SW]) const { gstore<SW>(field + q * SW, v); }
+    __device__ __forceinline__ void st_own_n(FRef<real> f, const real (&v)[SY]) const { st_slots<SY>(f, v); }
+    __device__ __forceinline__ void st_own_x(FRef<real> f, const real (&v)[SW]) const { st_slots<SW>(f, v); }
     // every lane gets the whole vector (the 4*SY / 4*SW words are read by all four lanes alike)
-    __device__ __forceinline__ void ld_rep_n(const real *field, real (&v)[N]) const {
+    __device__ __forceinline__ void ld_rep_n(FRef<real> f, real (&v)[N]) const {
         real w[4 * SY];
-        gload<4 * SY>(field, w);
+        ld_field<SY>(f, w);
 #pragma unroll
         for (int k = 0; k < N; ++k) v[k] = w[C::pn(k)];
     }
-    __device__ __forceinline__ void ld_repx_of_n(const real *field, real (&v)[NX]) const {   // x part of an n-vector
+    __device__ __forceinline__ void ld_repx_of_n(FRef<real> f, real (&v)[NX]) const {   // x part of an n-vector
         real w[4 * SY];
-        gload<4 * SY>(field, w);
+        ld_field<SY>(f, w);
 #pragma unroll
         for (int k = 0; k < NX; ++k) v[k] = w[C::pn(k)];
     }
-    __device__ __forceinline__ void ld_rep_x(const real *field, real (&v)[NX]) const {
+    __device__ __forceinline__ void ld_rep_x(FRef<real> f, real (&v)[NX]) const {
         real w[4 * SW];
-        gload<4 * SW>(field, w);
+        ld_field<SW>(f, w);
 #pragma unroll
         for (int r = 0; r < NX; ++r) v[r] = w[C::px(r)];
+    }
+    // slot c of L (QCfg::lbase) of this record, the chunk lane ql stores
+    __device__ __forceinline__ real *lchunk(real *rp, int s, int c, int ql) const {
+        return rp + C::w(C::oL + C::lbase(s) + c * C::lstride(s)) + 4 * ql;
     }
     // own elements out of a vector every lane holds (k = 4m + q; 0 where there is none)
     template <int LEN, int SL>
@@ -346,11 +472,14 @@ struct Quad {
     // ---- bound rows (QCfg::oUS): the control this lane owns is ju = (q - NX) mod 4, if that is < NU
     __device__ __forceinline__ int own_ju() const { return (q - NX) & 3; }
     __device__ __forceinline__ void ld_own_us(const real *rp, real &lu, real &ll, real &bu, real &bl) const {
-        gld4(rp + C::oUS + 4 * q, lu, ll, bu, bl);
+        gld4(rp + C::w(C::oUS.h) + 4 * q, lu, ll, bu, bl);
+    }
+    __device__ __forceinline__ void st_own_us(real *rp, real lu, real ll, real bu, real bl) const {
+        gst4(rp + C::w(C::oUS.h) + 4 * q, lu, ll, bu, bl);
     }
     __device__ __forceinline__ void ld_rep_us(const real *rp, real (&lu)[NU], real (&ll)[NU], real (&bu)[NU], real (&bl)[NU]) const {
         real w[16];
-        gload<16>(rp + C::oUS, w);
+        ld_field<4>(rp + C::oUS, w);
 #pragma unroll
         for (int ju = 0; ju < NU; ++ju) {
             const int ql = (NX + ju) & 3;
@@ -418,7 +547,7 @@ struct Quad {
                     const real *lb = glam + T * NX + t * 2 * NU;
                     const real a0 = lb[jc], a1 = lb[NU + jc], a2 = guhi[t * st_u + jc], a3 = gulo[t * st_u + jc];
                     const bool has = ju < NU;
-                    gst4(rp + C::oUS + 4 * q, has ? a0 : real(0), has ? a1 : real(0), has ? a2 : real(0), has ? a3 : real(0));
+                    st_own_us(rp, has ? a0 : real(0), has ? a1 : real(0), has ? a2 : real(0), has ? a3 : real(0));
                 }
                 if (dyn && have_c) ld_own_ext<NX>(gc + t * NX, vx);
                 else {
@@ -959,7 +1088,7 @@ struct Quad {
 #pragma unroll
                     for (int c = 0; c <= s; ++c)
                         if (C::lanes_of(s) == 4 || q < C::lanes_of(s))
-                            gst4(rp + C::oL + C::lbase(s) + c * 4 * C::lanes_of(s) + 4 * q, H[C::hidx(s, 4 * c)],
+                            gst4(lchunk(rp, s, c, q), H[C::hidx(s, 4 * c)],
                                  H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
                 real yo[SY];
                 own_of<N, SY>(Y, yo);
@@ -1028,7 +1157,7 @@ struct Quad {
                 for (int c = 0; c <= s; ++c) {
                     // lanes without a real row re-read lane 0's words (unconditional load, values unused)
                     const int ql = (C::lanes_of(s) == 4 || q < C::lanes_of(s)) ? q : 0;
-                    gld4(rp + C::oL + C::lbase(s) + c * 4 * C::lanes_of(s) + 4 * ql, H[C::hidx(s, 4 * c)],
+                    gld4(lchunk(rp, s, c, ql), H[C::hidx(s, 4 * c)],
                          H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
                 }
             real yo[SY];
@@ -1206,7 +1335,7 @@ struct Quad {
 #pragma unroll
                 for (int c = 0; c <= s; ++c) {
                     const int ql = (C::lanes_of(s) == 4 || q < C::lanes_of(s)) ? q : 0;
-                    gld4(rp + C::oL + C::lbase(s) + c * 4 * C::lanes_of(s) + 4 * ql, H[C::hidx(s, 4 * c)],
+                    gld4(lchunk(rp, s, c, ql), H[C::hidx(s, 4 * c)],
                          H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
                 }
             real Y[N];
@@ -1412,7 +1541,7 @@ struct Quad {
                     lln = c < 0 ? real(0) : c;
                 }
                 if (isub && active) {
-                    if (dual) gst4(rp + C::oUS + 4 * q, lun, lln, bu, bl);
+                    if (dual) st_own_us(rp, lun, lln, bu, bl);
                     if (write_out) {
                         glam[T * NX + t * 2 * NU + ju] = lun;
                         glam[T * NX + t * 2 * NU + NU + ju] = lln;

@@ -125,7 +125,8 @@ size_t alqp_lds_bytes(const AlqpDims *dims, int is_f64);
 int alqp_qps_per_wave(const AlqpDims *dims, int is_f64);
 /* Bytes of device workspace the quad variant of alqp_solve_lin needs for these dims
  * (0 if (nx,nu) is not instantiated). The caller allocates; contents need not be kept
- * between calls. */
+ * between calls. Layout: fp32 [ceil(B/2)][T][RECW/16][2][16] (the records of instances 2i, 2i+1
+ * interleaved in 64-byte blocks), fp64 [B][T][RECW]. */
 size_t alqp_workspace_bytes(const AlqpDims *dims, int is_f64);
 
 /*
