@@ -60,7 +60,7 @@ ALQP_EXIT_IN_KERNEL = 16
 ALQP_E_COOP = -4
 VARIANT_AUTO, VARIANT_TEAM, VARIANT_QUAD = 0, 1, 2
 
-ERRORS = {-1: "bad argument", -2: "unsupported (nx, nu) or horizon does not fit in LDS",
+ERRORS = {-1: "bad argument", -2: "unsupported (nx, nu), or horizon / batch beyond what the requested kernel can hold or address",
           -3: "kernel launch failed", -4: "grid too large for a cooperative launch"}
 
 _P = C.c_void_p

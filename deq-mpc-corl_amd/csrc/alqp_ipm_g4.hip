@@ -85,9 +85,9 @@ static int launch_kernel(const IpmArgs<real> &a, const real *lams, const real *s
 template <typename real, int NX, int NU>
 static int launch(IpmArgs<real> a, const real *lams, const real *slacks, bool backward, hipStream_t stream) {
     using S = Solver<real, NX, NU, kSlots, GpuX<real>>;
-    // what the kernel's 32-bit lane indices can address (element offsets inside one instance's strided inputs)
-    const long span = (long)a.T * (a.sC_t > a.sF_t ? a.sC_t : a.sF_t);
-    if (a.T > S::TMAX || a.T < 2 || span >= (1L << 31)) return ALQP_E_UNSUPPORTED;
+    // what the kernel's 32-bit byte offsets can address inside one instance's strided inputs
+    if (a.T > S::TMAX || !resident_addressable(a.T, NX, NU, (int)sizeof(real), a.sC_t, a.sF_t, a.sf_t))
+        return ALQP_E_UNSUPPORTED;
     const size_t lds = (size_t)S::lds_words(a.T) * sizeof(real);
     if (lds > kLdsMax) return ALQP_E_UNSUPPORTED;
     a.ws_words = Lay<real, NX, NU>(a.T, true).total;

@@ -416,7 +416,11 @@ typedef struct AlqpIpmParams {
  *    the Schur factor in LDS; HBM traffic = the inputs once + the best iterate when it improves) whenever the horizon
  *    fits its register slots (T <= 20), else the size-generic kernel with automatic factor placement;
  * 1 / 2: the size-generic kernel (vectors in the workspace) with the Schur factor in LDS / in the workspace;
- * 3: the register/LDS-resident kernel, ALQP_E_UNSUPPORTED when the problem does not fit it. */
+ * 3: the register/LDS-resident kernel, ALQP_E_UNSUPPORTED when the problem does not fit it.
+ * The resident kernel addresses Cd / c, F and f with 32-bit byte offsets from each instance's base, so it fits only
+ * while the last element it reads of each array starts below 4 GiB: (T-1)*sC_t + n - 1, (T-2)*sF_t + nx*n - 1 and
+ * (T-2)*sf_t + nx - 1 elements, times sizeof(real). Time-major data (qp_wrapper.MPC) passes that at B ~ 135 k in fp64
+ * and ~ 270 k in fp32 for (T, nx, nu) = (20, 13, 4); beyond it variant 0 runs the generic kernel. */
 #define ALQP_IPM_VARIANT_AUTO 0
 #define ALQP_IPM_VARIANT_GENERIC_LDS 1
 #define ALQP_IPM_VARIANT_GENERIC_WS 2

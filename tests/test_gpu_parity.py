@@ -393,15 +393,17 @@ def test_variants_agree_at_headline_size():
     assert float(err.median()) < 2e-5
 
 
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
 @pytest.mark.parametrize("exit_mode", ["fixed", "reference"])
-def test_backward_quad_workspace_equals_team_factor(exit_mode):
+def test_backward_quad_workspace_equals_team_factor(exit_mode, dtype):
     """Gradients w.r.t. q and diag(Q) through the two backward routes - the quad solve's
     workspace as factor (alqp_backward_ws) and the team kernel's packed factor (alqp_backward) -
-    agree on a (13,4) batch; both implement NewtonAL.backward (al_utils.py:578-615)."""
+    agree on a (13,4) batch; both implement NewtonAL.backward (al_utils.py:578-615). In fp32 the quad
+    records are interleaved in instance pairs (B = 37: the last pair is half used)."""
     from deq_mpc_corl_amd import MPC, AffineDynamics, QuadCost, synthetic_problem
     from deq_mpc_corl_amd.backend import HipBackend
 
-    dt = torch.float64
+    dt = TD[dtype]
     B, T, nx, nu = 37, 9, 13, 4
     p = synthetic_problem(B, T, nx, nu, seed=31, dtype=dt, device=DEV, active=True)
     g = torch.Generator(device="cpu").manual_seed(2)
@@ -412,6 +414,12 @@ def test_backward_quad_workspace_equals_team_factor(exit_mode):
         if be is None:
             be = HipBackend()
             be.default_variant = "team"
+        else:
+            # the host logic keeps the factor in the quad workspace only from QUAD_MIN_BATCH (4096) on; below it both
+            # routes would run the team kernels and the packed factor
+            be.QUAD_MIN_BATCH = 0
+            bw_ws, calls = be.backward_ws, []
+            be.backward_ws = lambda *a, _f=bw_ws, _c=calls: (_c.append(1), _f(*a))[1]
         mpc = MPC(nx, nu, T, u_lower=p.u_lo, u_upper=p.u_hi, n_batch=B, dtype=dt, exit_mode=exit_mode, backend=be)
         if name == "team":
             # hide the quad route from the host logic (hasattr check)
@@ -429,11 +437,25 @@ def test_backward_quad_workspace_equals_team_factor(exit_mode):
         cost = QuadCost(torch.diag_embed(Qd), q, torch.zeros(B, T, device=DEV, dtype=dt))
         x, u, _ = mpc(p.x0, cost, dyn, dyn.jac, x_init=p.z0[..., :nx].clone(), u_init=p.z0[..., nx:].clone())
         ((x * wx).sum() + (u * wu).sum()).backward()
+        if name == "quad":
+            assert calls, "the quad route did not run alqp_backward_ws"
         grads[name] = (q.grad.clone(), Qd.grad.clone(), x.detach().clone())
-    assert torch.allclose(grads["quad"][2], grads["team"][2], atol=1e-5)
     sq = float(grads["team"][0].abs().max())
-    assert float((grads["quad"][0] - grads["team"][0]).abs().max()) < 1e-6 * sq
-    assert float((grads["quad"][1] - grads["team"][1]).abs().max()) < 1e-6 * float(grads["team"][1].abs().max())
+    eq = float((grads["quad"][0] - grads["team"][0]).abs().max()) / sq
+    eQ = float((grads["quad"][1] - grads["team"][1]).abs().max()) / float(grads["team"][1].abs().max())
+    ex = float((grads["quad"][2] - grads["team"][2]).abs().max())
+    print(f"quad vs team backward {dtype} {exit_mode}: x {ex:.2e}, q_grad {eq:.2e}, Qd_grad {eQ:.2e}")
+    if dtype == "f64":
+        assert torch.allclose(grads["quad"][2], grads["team"][2], atol=1e-5)
+        assert eq < 1e-6
+        assert eQ < 1e-6
+    else:
+        assert ex < FP32_QUAD_TEAM_TOL["x"] and eq < FP32_QUAD_TEAM_TOL["grad"] and eQ < FP32_QUAD_TEAM_TOL["grad"]
+
+
+# fp32 bounds of test_backward_quad_workspace_equals_team_factor (the two routes round differently in the solve);
+# measured on the MI355X: x 4.0e-5, q_grad 6.1e-8, Qd_grad 2.0e-5 (relative to max |grad|)
+FP32_QUAD_TEAM_TOL = {"x": 2e-4, "grad": 1e-4}
 
 
 @pytest.mark.parametrize("cfg", ["pendulum T=5 B=4096 f32 (BASELINE config 2)", "(8,2) T=10 B=8192 f32 (config 3)",

@@ -178,6 +178,12 @@ def test_ip_at_scale_properties(dtype, variant):
     f64 = dtype == "f64"
     if f64:
         assert int((r1["info"] != 0).sum()) == 0
+    else:
+        # fp32 trips non-positive Schur pivots in many instances (the kernels replace them by their magnitude; the C
+        # oracle's fp32 run trips them too). Measured on the MI355X at this configuration: 4565 of 8192 instances on the
+        # resident kernel, 6495 on the generic one; the bound holds that count.
+        tripped = int((r1["info"] != 0).sum())
+        assert tripped <= {"resident": 4700, "generic_ws": 6700, "generic_lds": 6700}[variant], tripped
     assert float(r1["resid"].max()) < (1e-10 if f64 else 5e-2), float(r1["resid"].max())
     sel = torch.arange(0, B, B // 32, device="cuda:0")[:32]
     c = lambda a: a.index_select(0, sel).cpu().numpy()
