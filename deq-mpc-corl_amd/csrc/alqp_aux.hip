@@ -1,0 +1,402 @@
+// alqp_aux.hip - the size-generic helper kernels of the launch-per-step routes (merit, line-search pick, dual update,
+// batch-global exit test; one wavefront per instance) with their C ABI.
+#include <hip/hip_runtime.h>
+
+#include "alqp_launch.hpp"   // dims_ok
+#include "mi_alqp.h"
+
+namespace alqp {
+
+// ---- size-generic helper kernels (one wavefront per instance) ----------------------
+template <typename real>
+__device__ inline real wave_sum(real v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <typename real>
+struct AuxArgs {
+    int B, T, nx, nu, K, n_ls;
+    const real *zc, *xnext, *x0, *lam, *rho, *Qd, *q, *ulo, *uhi;
+    long sb_u, st_u;
+    real *phi, *rnorm2;
+    // pick
+    const real *phi_all, *d;
+    real *phi_prev, *z;
+    int *k_out, *accept_out;
+    // dual
+    real *lam_io, *rho_io;
+    real rho_scale;
+    // obstacle rows (nullable): centres [B][T][nobs][3], radius^2
+    const real *obs;
+    int nobs;
+    real obs_r2;
+    int no_init;   // state-estimator row set: the initial-state rows (row block T-1) do not exist
+};
+
+// c_k = r^2 - |x_t[0:3] - o_k|^2 for obstacle row e = t*nobs + k of instance b (al_utils.py:313-323)
+template <typename real>
+__device__ inline real obs_row(const AuxArgs<real> &a, const real *z, int b, int e) {
+    const int t = e / a.nobs, n = a.nx + a.nu;
+    const real *o = a.obs + ((size_t)b * a.T * a.nobs + e) * 3;
+    const real d0 = z[t * n] - o[0], d1 = z[t * n + 1] - o[1], d2 = z[t * n + 2] - o[2];
+    return a.obs_r2 - (d0 * d0 + d1 * d1 + d2 * d2);
+}
+
+// merit of candidate kk for instance b (al_utils.py:73-77), block = (kk, b)
+template <typename real>
+__global__ __launch_bounds__(64) void k_merit(AuxArgs<real> a) {
+    const int lane = threadIdx.x;
+    const int b = blockIdx.x % a.B, kk = blockIdx.x / a.B;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx;
+    const real *z = a.zc + ((size_t)kk * a.B + b) * T * n;
+    const real *xn = a.xnext + ((size_t)kk * a.B + b) * (T - 1) * nx;
+    const int nit = 2 * nu + a.nobs;   // inequality rows per stage
+    const real *lam = a.lam + (size_t)b * (neq + T * nit);
+    const real *Qd = a.Qd + (size_t)b * T * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real rho = a.rho[b];
+    real acc = 0, sq = 0;
+    for (int e = lane; e < T * n; e += 64) {
+        int t = e / n, j = e - t * n;
+        real v = z[e];
+        acc += (real(0.5) * Qd[e] * v + q[e]) * v;
+        if (j >= nx) {
+            int ju = j - nx;
+            real vu = v - uhi[t * a.st_u + ju], vl = -v + ulo[t * a.st_u + ju];
+            real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+            int ru = neq + t * nit + ju;
+            acc += lam[ru] * vu + lam[ru + nu] * vl;
+            sq += cu * cu + cl * cl;
+        }
+    }
+    for (int e = lane; e < T * a.nobs; e += 64) {
+        const real ck = obs_row(a, z, b, e), cp = ck > 0 ? ck : real(0);
+        acc += lam[neq + (e / a.nobs) * nit + 2 * nu + e % a.nobs] * ck;
+        sq += cp * cp;
+    }
+    const int neq_rows = a.no_init ? neq - nx : neq;
+    for (int e = lane; e < neq_rows; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        acc += lam[e] * r;
+        sq += r * r;
+    }
+    acc = wave_sum(acc);
+    sq = wave_sum(sq);
+    if (lane == 0) {
+        a.phi[(size_t)kk * a.B + b] = acc + real(0.5) * rho * sq;
+        if (a.rnorm2) a.rnorm2[(size_t)kk * a.B + b] = sq;
+    }
+}
+
+// The whole line search of one Newton step in ONE launch (nonlinear-caller mode at scale): the merits of
+// the n_ls candidates z + 2^-k d (al_utils.py:618-633; x_next of every candidate was evaluated by the
+// caller's dynamics: xnext_all [n_ls][B][T-1][nx]), first-argmin with NaN winning like torch.min, strict
+// accept, z <- z + alpha d in place, phi_prev <- phi_min regardless (:569), rnorm2 <- sum r+^2 of the
+// chosen candidate when accepted. One wavefront per instance: it reads z, d once (not the 20-fold stack
+// the reference materialises) and its 20 x_next slabs; everything else comes from registers.
+template <typename real>
+__global__ __launch_bounds__(64) void k_merit_pick(AuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, nit = 2 * nu + a.nobs;
+    real *z = a.z + (size_t)b * T * n;
+    const real *d = a.d + (size_t)b * T * n;
+    const real *lam = a.lam + (size_t)b * (neq + T * nit);
+    const real *Qd = a.Qd + (size_t)b * T * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real rho = a.rho[b];
+    real acc[20], sq[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) { acc[k] = 0; sq[k] = 0; }
+    // cost + bound rows: every lane walks its elements once, all candidates from registers
+    for (int e = lane; e < T * n; e += 64) {
+        const int t = e / n, j = e - t * n;
+        const real zv = z[e], dv = d[e], Qv = Qd[e], qv = q[e];
+        real bu = 0, bl = 0, lu = 0, ll = 0;
+        const bool isu = j >= nx;
+        if (isu) {
+            bu = uhi[t * a.st_u + j - nx]; bl = ulo[t * a.st_u + j - nx];
+            lu = lam[neq + t * nit + j - nx]; ll = lam[neq + t * nit + nu + j - nx];
+        }
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            const real v = zv + alpha * dv;
+            acc[k] += (real(0.5) * Qv * v + qv) * v;
+            if (isu) {
+                const real vu = v - bu, vl = -v + bl;
+                const real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+                acc[k] += lu * vu + ll * vl;
+                sq[k] += cu * cu + cl * cl;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    // equality rows: r = x_{t+1}(candidate) - xnext_k, init rows x_0 - x0
+    for (int e = lane; e < (a.no_init ? neq - nx : neq); e += 64) {
+        const int t = e / nx, i = e - t * nx;
+        const real le = lam[e];
+        const int zi = (t < T - 1) ? (t + 1) * n + i : i;
+        const real zv = z[zi], dv = d[zi];
+        const real x0v = (t < T - 1) ? real(0) : a.x0[(size_t)b * nx + i];
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            if (k < a.n_ls) {
+                const real ref = (t < T - 1) ? a.xnext[(((size_t)k * a.B + b) * (T - 1) + t) * nx + i] : x0v;
+                const real r = zv + alpha * dv - ref;
+                acc[k] += le * r;
+                sq[k] += r * r;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    // obstacle rows (Obstacle_MPC): c_k at the candidate's position
+    for (int e = lane; e < T * a.nobs; e += 64) {
+        const int t = e / a.nobs;
+        const real *o = a.obs + ((size_t)b * T * a.nobs + e) * 3;
+        const real lk = lam[neq + t * nit + 2 * nu + e % a.nobs];
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            const real d0 = z[t * n] + alpha * d[t * n] - o[0], d1 = z[t * n + 1] + alpha * d[t * n + 1] - o[1],
+                       d2 = z[t * n + 2] + alpha * d[t * n + 2] - o[2];
+            const real ck = a.obs_r2 - (d0 * d0 + d1 * d1 + d2 * d2), cp = ck > 0 ? ck : real(0);
+            acc[k] += lk * ck;
+            sq[k] += cp * cp;
+            alpha *= real(0.5);
+        }
+    }
+    int kbest = 0;
+    real best = 0, sqbest = 0;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) {
+        if (k < a.n_ls) {
+            const real s2 = wave_sum(sq[k]);
+            const real v = wave_sum(acc[k]) + real(0.5) * rho * s2;
+            if (a.phi) a.phi[(size_t)k * a.B + b] = v;     // (all lanes hold the same value)
+            if (k == 0) { best = v; sqbest = s2; }
+            else if (!(best != best) && (v != v || v < best)) { best = v; kbest = k; sqbest = s2; }
+        }
+    }
+    const real prev = a.phi_prev[b];
+    const bool ok = best < prev;
+    if (ok) {
+        const real alpha = real(1) / real(1 << kbest);
+        for (int e = lane; e < T * n; e += 64) z[e] += alpha * d[e];
+    }
+    if (lane == 0) {
+        a.phi_prev[b] = best;
+        if (a.k_out) a.k_out[b] = kbest;
+        if (a.accept_out) a.accept_out[b] = ok ? 1 : 0;
+        if (a.rnorm2 && ok) a.rnorm2[b] = sqbest;
+    }
+}
+
+// line-search decision + update (al_utils.py:634-641), block = instance
+template <typename real>
+__global__ __launch_bounds__(64) void k_pick(AuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int Tn = a.T * (a.nx + a.nu);
+    int kbest = 0;
+    real best = a.phi_all[b];
+    for (int k = 1; k < a.n_ls; ++k) {
+        real v = a.phi_all[(size_t)k * a.B + b];
+        if (!(best != best) && (v != v || v < best)) { best = v; kbest = k; }
+    }
+    const real prev = a.phi_prev[b];
+    const bool acc = best < prev;
+    const real alpha = acc ? real(1) / real(1 << kbest) : real(0);
+    real *z = a.z + (size_t)b * Tn;
+    const real *d = a.d + (size_t)b * Tn;
+    if (acc)
+        for (int e = lane; e < Tn; e += 64) z[e] += alpha * d[e];
+    __syncthreads();
+    if (lane == 0) {
+        a.phi_prev[b] = best;
+        if (a.k_out) a.k_out[b] = kbest;
+        if (a.accept_out) a.accept_out[b] = acc ? 1 : 0;
+    }
+}
+
+// dual update + projection + rho growth (AL_mpc.py:315-317,325), block = instance
+template <typename real>
+__global__ __launch_bounds__(64) void k_dual(AuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx;
+    const real *z = a.zc + (size_t)b * T * n;
+    const real *xn = a.xnext + (size_t)b * (T - 1) * nx;
+    const int nit = 2 * nu + a.nobs;
+    real *lam = a.lam_io + (size_t)b * (neq + T * nit);
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real rho = a.rho_io[b];
+    for (int e = lane; e < (a.no_init ? neq - nx : neq); e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        lam[e] += rho * r;
+    }
+    for (int e = lane; e < T * nu; e += 64) {
+        int t = e / nu, j = e - t * nu;
+        real u = z[t * n + nx + j];
+        int ru = neq + t * nit + j, rl = ru + nu;
+        real v1 = lam[ru] + rho * (u - uhi[t * a.st_u + j]);
+        real v2 = lam[rl] + rho * (-u + ulo[t * a.st_u + j]);
+        lam[ru] = v1 < 0 ? real(0) : v1;
+        lam[rl] = v2 < 0 ? real(0) : v2;
+    }
+    for (int e = lane; e < T * a.nobs; e += 64) {
+        const int r = neq + (e / a.nobs) * nit + 2 * nu + e % a.nobs;
+        const real v = lam[r] + rho * obs_row(a, z, b, e);
+        lam[r] = v < 0 ? real(0) : v;
+    }
+    __syncthreads();
+    if (lane == 0) a.rho_io[b] = rho * a.rho_scale;
+}
+
+// batch-global exit test of the Newton loop, taken on the device (al_utils.py:551-564)
+__global__ void k_exit_test(const double *sumsq, double *ctl, int mode, double tol) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double nw = sqrt(sumsq[0]);
+    if (mode == 0) {
+        ctl[0] = 0.0;
+        ctl[1] = 0.0;
+        ctl[2] = nw;
+    } else if (ctl[0] == 0.0) {
+        ctl[1] += 1.0;
+        const double old = ctl[2];
+        if (nw < tol || fabs(old - nw) / nw < tol) ctl[0] = 1.0;   // nw = inf (a tripped instance): NaN, no exit
+        else ctl[2] = nw;
+    }
+}
+
+template <typename real>
+int merit_impl(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+               const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+               const void *u_hi, long sb_u, long st_u, void *phi, void *rnorm2, void *stream,
+               const AlqpObstacles *obs = nullptr) {
+    if (!dims_ok(dims) || K < 1 || !zc || !xnext || !x0 || !lam || !rho || !Qd || !q || !u_lo || !u_hi || !phi)
+        return ALQP_E_BADARG;
+    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
+    AuxArgs<real> a = {};
+    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
+    if (obs) a.no_init = obs->state_estimator;
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu; a.K = K;
+    a.zc = (const real *)zc; a.xnext = (const real *)xnext; a.x0 = (const real *)x0;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.phi = (real *)phi; a.rnorm2 = (real *)rnorm2;
+    hipLaunchKernelGGL(k_merit<real>, dim3((unsigned)((size_t)K * dims->B)), dim3(64), 0,
+                       (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int merit_pick_impl(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                    const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                    const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs, void *z, void *phi_prev,
+                    void *rnorm2, void *phi_all, int *k_out, int *accept_out, void *stream) {
+    if (!dims_ok(dims) || n_ls < 1 || n_ls > 20 || !d || !xnext_all || !x0 || !lam || !rho || !Qd || !q || !u_lo ||
+        !u_hi || !z || !phi_prev)
+        return ALQP_E_BADARG;
+    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
+    AuxArgs<real> a = {};
+    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
+    if (obs) a.no_init = obs->state_estimator;
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu; a.n_ls = n_ls;
+    a.d = (const real *)d; a.xnext = (const real *)xnext_all; a.x0 = (const real *)x0;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.z = (real *)z; a.phi_prev = (real *)phi_prev; a.rnorm2 = (real *)rnorm2; a.phi = (real *)phi_all;
+    a.k_out = k_out; a.accept_out = accept_out;
+    hipLaunchKernelGGL(k_merit_pick<real>, dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int pick_impl(const AlqpDims *dims, int n_ls, const void *phi, void *phi_prev, const void *d, void *z,
+              int *k_out, int *accept_out, void *stream) {
+    if (!dims_ok(dims) || n_ls < 1 || !phi || !phi_prev || !d || !z) return ALQP_E_BADARG;
+    AuxArgs<real> a = {};
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu; a.n_ls = n_ls;
+    a.phi_all = (const real *)phi; a.phi_prev = (real *)phi_prev; a.d = (const real *)d; a.z = (real *)z;
+    a.k_out = k_out; a.accept_out = accept_out;
+    hipLaunchKernelGGL(k_pick<real>, dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int dual_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *x0, const void *u_lo,
+              const void *u_hi, long sb_u, long st_u, void *lam, void *rho, double rho_scale,
+              void *stream, const AlqpObstacles *obs = nullptr) {
+    if (!dims_ok(dims) || !z || !xnext || !x0 || !u_lo || !u_hi || !lam || !rho) return ALQP_E_BADARG;
+    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
+    AuxArgs<real> a = {};
+    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
+    if (obs) a.no_init = obs->state_estimator;
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu;
+    a.zc = (const real *)z; a.xnext = (const real *)xnext; a.x0 = (const real *)x0;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.lam_io = (real *)lam; a.rho_io = (real *)rho; a.rho_scale = (real)rho_scale;
+    hipLaunchKernelGGL(k_dual<real>, dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+}  // namespace alqp
+
+extern "C" {
+
+int alqp_exit_test(const double *sumsq, double *ctl, int mode, double tol, void *stream) {
+    if (!sumsq || !ctl || (mode != 0 && mode != 1)) return ALQP_E_BADARG;
+    hipLaunchKernelGGL(alqp::k_exit_test, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, ctl, mode, tol);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+#define ALQP_DEFINE_AUX(SFX, REAL)                                                                    \
+    int alqp_merit_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,              \
+                         const void *x0, const void *lam, const void *rho, const void *Qd,            \
+                         const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,     \
+                         void *phi, void *rnorm2, void *stream) {                                     \
+        return alqp::merit_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u,      \
+                                      st_u, phi, rnorm2, stream);                                     \
+    }                                                                                                 \
+    int alqp_merit_obs_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,          \
+                             const void *x0, const void *lam, const void *rho, const void *Qd,        \
+                             const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u, \
+                             const AlqpObstacles *obs, void *phi, void *rnorm2, void *stream) {       \
+        return alqp::merit_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u,      \
+                                      st_u, phi, rnorm2, stream, obs);                                \
+    }                                                                                                 \
+    int alqp_merit_pick_##SFX(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all,   \
+                              const void *x0, const void *lam, const void *rho, const void *Qd,       \
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u, \
+                              const AlqpObstacles *obs, void *z, void *phi_prev, void *rnorm2,        \
+                              void *phi_all, int *k_out, int *accept_out, void *stream) {             \
+        return alqp::merit_pick_impl<REAL>(dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, u_lo, u_hi, \
+                                           sb_u, st_u, obs, z, phi_prev, rnorm2, phi_all, k_out,      \
+                                           accept_out, stream);                                       \
+    }                                                                                                 \
+    int alqp_linesearch_pick_##SFX(const AlqpDims *dims, int n_ls, const void *phi, void *phi_prev,   \
+                                   const void *d, void *z, int *k_out, int *accept_out,               \
+                                   void *stream) {                                                    \
+        return alqp::pick_impl<REAL>(dims, n_ls, phi, phi_prev, d, z, k_out, accept_out, stream);     \
+    }                                                                                                 \
+    int alqp_dual_update_##SFX(const AlqpDims *dims, const void *z, const void *xnext,                \
+                               const void *x0, const void *u_lo, const void *u_hi, long sb_u,         \
+                               long st_u, void *lam, void *rho, double rho_scale, void *stream) {     \
+        return alqp::dual_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, lam, rho, rho_scale, \
+                                     stream);                                                         \
+    }                                                                                                 \
+    int alqp_dual_update_obs_##SFX(const AlqpDims *dims, const void *z, const void *xnext,            \
+                                   const void *x0, const void *u_lo, const void *u_hi, long sb_u,     \
+                                   long st_u, const AlqpObstacles *obs, void *lam, void *rho,         \
+                                   double rho_scale, void *stream) {                                  \
+        return alqp::dual_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, lam, rho, rho_scale, \
+                                     stream, obs);                                                    \
+    }
+
+ALQP_DEFINE_AUX(f32, float)
+ALQP_DEFINE_AUX(f64, double)
+
+}  // extern "C"

@@ -1,0 +1,365 @@
+// alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
+// and fp64 in one object.
+#include <hip/hip_runtime.h>
+
+#include "alqp_team.hpp"
+#include "alqp_dims.hpp"
+#include "alqp_launch.hpp"
+
+namespace alqp {
+
+#ifdef ALQP_PHASE_TIMING
+__device__ unsigned long long g_team_cycles[8];   // debug build only (tools/team_timing.py)
+#endif
+// ---- fused LinDx solve -------------------------------------------------------------
+// OCC: wavefronts per SIMD the register allocation is capped for. 2 (256 registers) lets a CU hold the 8 teams its
+// LDS has room for, but costs 80 B (fp32) / 252 B (fp64) of scratch per lane at (13,4); 1 (no cap) has no scratch.
+// Measured (profiles/r02/experiments): fp64 is faster uncapped at every batch the team kernels see (B = 200: 1.27 ->
+// 1.22 ms, B = 2048: 3.43 -> 2.85 ms); fp32 only while there is at most one wavefront per SIMD anyway (B = 200: 0.84 ->
+// 0.80 ms, B = 1024: 0.91 -> 0.87 ms; B = 2048: 1.07 against 1.71 ms). dispatch_solve() picks accordingly.
+// The TRACE instantiations (tests only) are never capped: with their extra live pointers the capped fp64 builds spill ~70-150
+// registers, and this hipcc (ROCm 7.2) can place such a spill store at the head of a divergent loop's exit block IN FRONT OF the
+// `s_or_b64 exec` that re-enables the lanes - the store then runs with EXEC = 0 and the reload returns stale scratch. Seen once
+// (k_solve_lin<double,12,4,true,2>: the zs base offset spilled after the `for (e = li; e < T*N; e += G)` load loop, every row
+// of the returned z one repeated value); the uncapped builds have no spills (checked per kernel: tools/spill_report.py).
+template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
+__global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceArgs<real> tr) {
+    if (a.skip && *a.skip != 0.0) return;  // block-uniform, before any barrier
+    using C = Cfg<real, NX, NU>;
+    constexpr int G = C::G, N = C::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    real *smem = reinterpret_cast<real *>(smem_raw);
+    const int lane = threadIdx.x, team = lane / G, li = lane % G;
+    const int b_raw = blockIdx.x * C::QPW + team;
+    const bool active = b_raw < a.B;
+    const int b = active ? b_raw : a.B - 1;
+    const int T = a.T, M = C::M(T), neq = T * NX;
+
+    Team<real, NX, NU> tm;
+#ifdef ALQP_PHASE_TIMING
+    for (int i = 0; i < 8; ++i) tm.tacc[i] = 0;
+    tm.stamp(-1);
+#endif
+    tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
+    tm.gQd = a.Qd + (size_t)b * T * N;
+    tm.gq = a.q + (size_t)b * T * N;
+    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
+    tm.gc = a.c + (size_t)b * (T - 1) * NX;
+    tm.gx0 = a.x0 + (size_t)b * NX;
+    tm.gulo = a.ulo + (size_t)b * a.sb_u;
+    tm.guhi = a.uhi + (size_t)b * a.sb_u;
+    tm.st_u = a.st_u;
+
+    real *gz = a.z + (size_t)b * T * N;
+    tm.lams = a.lam + (size_t)b * M;  // multipliers stay in global memory (L2), updated in place
+    for (int e = li; e < T * N; e += G) tm.zs[e] = gz[e];
+    tm.rho = a.rho[b];
+    real phi_prev = a.phi[b];
+    wave_sync();
+    tm.residual_sweep();
+
+    int step_id = 0;
+    const bool ref_exit = (a.flags & ALQP_EXIT_IN_KERNEL) != 0;   // grid-uniform
+    int gphase = 0;
+    for (int it = 0; it < a.al_iter; ++it) {
+        if (a.flags & ALQP_INIT_MERIT) {
+            real p1[1];
+            tm.template merit_candidates<1>(p1, true);
+            phi_prev = p1[0];
+        }
+        double nrm_old = 0;
+        int n_done = 0;
+        if (ref_exit) {   // ||r+|| over the whole batch at the start of the Newton loop (al_utils.py:486)
+            const real r0 = tm.rplus2();
+            nrm_old = sqrt(grid_sum_ordered(wave_sum_leaders(exit_term(r0, tm.info), active && li == 0), a.exit_scratch, gphase));
+        }
+        for (int st = 0; st < a.max_newton; ++st, ++step_id) {
+            real *tg = nullptr;
+            if constexpr (TRACE) tg = (tr.g && active) ? tr.g + ((size_t)step_id * a.B + b) * T * N : nullptr;
+            tm.forward_sweep(tg);
+#ifdef ALQP_PHASE_TIMING
+            tm.stamp(-1);
+#endif
+            tm.backward_sweep();
+#ifdef ALQP_PHASE_TIMING
+            tm.stamp(4);
+#endif
+            if constexpr (TRACE) {
+                if (tr.d && active) {
+                    real *td = tr.d + ((size_t)step_id * a.B + b) * T * N;
+                    for (int e = li; e < T * N; e += G) td[e] = tm.ds[e];
+                }
+            }
+            real ph[20];
+            tm.template merit_candidates<20>(ph, false);
+#ifdef ALQP_PHASE_TIMING
+            tm.stamp(5);
+#endif
+            // first argmin, a NaN wins like torch.min (al_utils.py:634)
+            int kbest = 0;
+            real best = ph[0];
+            if (a.n_ls == 20) {
+#pragma unroll
+                for (int k = 1; k < 20; ++k) {
+                    if (!(best != best) && (ph[k] != ph[k] || ph[k] < best)) {
+                        best = ph[k];
+                        kbest = k;
+                    }
+                }
+            } else if constexpr (C::RB * C::NXP >= 20) {
+                // fewer candidates (tests): go through LDS (the Ft region is free here)
+                // instead of 20 hoisted lane masks
+                if (li == 0) {
+#pragma unroll
+                    for (int k = 0; k < 20; ++k) tm.Ft[k] = ph[k];
+                }
+                wave_sync();
+                for (int k = 1; k < a.n_ls; ++k) {
+                    real v = tm.Ft[k];
+                    if (!(best != best) && (v != v || v < best)) {
+                        best = v;
+                        kbest = k;
+                    }
+                }
+                wave_sync();
+                if (li < 20) tm.Ft[li] = 0;  // restore the constant zeros of the SYRK operand
+                wave_sync();
+            } else {
+#pragma unroll
+                for (int k = 1; k < 20; ++k) {
+                    if (k < a.n_ls && !(best != best) && (ph[k] != ph[k] || ph[k] < best)) {
+                        best = ph[k];
+                        kbest = k;
+                    }
+                }
+            }
+            const bool acc = best < phi_prev;
+            if constexpr (TRACE) {
+                if (active && li == 0) {
+                    if (tr.phi)
+#pragma unroll
+                        for (int k = 0; k < 20; ++k)
+                            if (k < a.n_ls) tr.phi[((size_t)step_id * a.n_ls + k) * a.B + b] = ph[k];
+                    if (tr.phi_prev) tr.phi_prev[(size_t)step_id * a.B + b] = phi_prev;
+                    if (tr.k) tr.k[(size_t)step_id * a.B + b] = kbest;
+                    if (tr.accept) tr.accept[(size_t)step_id * a.B + b] = acc ? 1 : 0;
+                }
+            }
+            const real alpha = acc ? real(1) / real(1 << kbest) : real(0);
+            for (int e = li; e < T * N; e += G) tm.zs[e] += alpha * tm.ds[e];
+            for (int e = li; e < neq; e += G) tm.req[e] += alpha * tm.seq[e];
+            wave_sync();
+#ifdef ALQP_PHASE_TIMING
+            tm.stamp(6);
+#endif
+            phi_prev = best;  // merit <- new_merit even when rejected (al_utils.py:569)
+            if (ref_exit) {   // al_utils.py:551-564, the same test alqp_exit_test takes between launches
+                const real r1 = tm.rplus2();
+                const double nw = sqrt(grid_sum_ordered(wave_sum_leaders(exit_term(r1, tm.info), active && li == 0), a.exit_scratch, gphase));
+                ++n_done;
+                if (nw < a.exit_tol || fabs(nrm_old - nw) / nw < a.exit_tol) break;
+                nrm_old = nw;
+            }
+        }
+        if (ref_exit && a.newton_counts && blockIdx.x == 0 && lane == 0) a.newton_counts[it] = grid_barrier_timed_out(a.exit_scratch) ? -1 : n_done;
+        if (a.flags & ALQP_DUAL_UPDATE) {
+            if (active) tm.dual_update();  // in-place on global lam: padding teams must not touch it
+            tm.rho *= a.rho_scale;
+        }
+    }
+
+    const real rn2 = tm.rplus2();
+    int bad = 0;
+    for (int e = li; e < T * N; e += G) {
+        real v = tm.zs[e];
+        bad |= !(v - v == real(0));
+    }
+    bad = team_or<G>(bad);
+#ifdef ALQP_PHASE_TIMING
+    tm.stamp(7);
+    if (lane == 0)
+        for (int i = 0; i < 8; ++i) atomicAdd(&g_team_cycles[i], tm.tacc[i]);
+#endif
+    if (active) {
+        for (int e = li; e < T * N; e += G) gz[e] = tm.zs[e];
+        if ((a.flags & ALQP_SAVE_FACTOR) && a.factor) {
+            real *gf = a.factor + (size_t)b * T * C::XT;
+            for (int e = li; e < T * C::XT; e += G) gf[e] = tm.Xp[e];
+        }
+        if (li == 0) {
+            a.rho[b] = tm.rho;
+            a.phi[b] = phi_prev;
+            if (a.rnorm2) a.rnorm2[b] = rn2;
+            if (a.info && tm.info && a.info[b] == 0) a.info[b] = tm.info;  // sticky: first failure of the solve
+            if (a.status) a.status[b] = bad ? 0 : 1;
+        }
+    }
+}
+
+// ---- one Newton direction (nonlinear-caller mode) ----------------------------------
+template <typename real, int NX, int NU>
+__global__ __launch_bounds__(64) void k_newton_step(StepArgs<real> a) {
+    using C = Cfg<real, NX, NU>;
+    constexpr int G = C::G, N = C::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    real *smem = reinterpret_cast<real *>(smem_raw);
+    const int lane = threadIdx.x, team = lane / G, li = lane % G;
+    const int b_raw = blockIdx.x * C::QPW + team;
+    const bool active = b_raw < a.B;
+    const int b = active ? b_raw : a.B - 1;
+    const int T = a.T, M = C::M(T) + T * a.nobs;
+
+    Team<real, NX, NU> tm;
+    tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
+    if (a.nobs > 0) { tm.gobs = a.obs + (size_t)b * T * a.nobs * 3; tm.nobs = a.nobs; tm.obs_r2 = a.obs_r2; }
+    tm.no_init = a.no_init != 0;
+    tm.gQd = a.Qd + (size_t)b * T * N;
+    tm.gq = a.q + (size_t)b * T * N;
+    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
+    tm.gc = nullptr;
+    tm.gx0 = a.x0 + (size_t)b * NX;
+    tm.gulo = a.ulo + (size_t)b * a.sb_u;
+    tm.guhi = a.uhi + (size_t)b * a.sb_u;
+    tm.st_u = a.st_u;
+    tm.gxnext = a.xnext + (size_t)b * (T - 1) * NX;
+    const real *gz = a.z + (size_t)b * T * N;
+    tm.lams = const_cast<real *>(a.lam) + (size_t)b * M;  // read-only here
+    for (int e = li; e < T * N; e += G) tm.zs[e] = gz[e];
+    tm.rho = a.rho[b];
+    wave_sync();
+    tm.forward_sweep((active && a.g_out) ? a.g_out + (size_t)b * T * N : nullptr);
+    tm.backward_sweep();
+    if (active) {
+        real *gd = a.d_out + (size_t)b * T * N;
+        for (int e = li; e < T * N; e += G) gd[e] = tm.ds[e];
+        if (a.factor) {
+            real *gf = a.factor + (size_t)b * T * C::XT;
+            for (int e = li; e < T * C::XT; e += G) gf[e] = tm.Xp[e];
+        }
+        if (li == 0 && a.info && tm.info && a.info[b] == 0) a.info[b] = tm.info;
+    }
+}
+
+// ---- backward of the implicit layer -------------------------------------------------
+template <typename real, int NX, int NU>
+__global__ __launch_bounds__(64) void k_backward(BwdArgs<real> a) {
+    using C = Cfg<real, NX, NU>;
+    constexpr int G = C::G, N = C::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    real *smem = reinterpret_cast<real *>(smem_raw);
+    const int lane = threadIdx.x, team = lane / G, li = lane % G;
+    const int b_raw = blockIdx.x * C::QPW + team;
+    const bool active = b_raw < a.B;
+    const int b = active ? b_raw : a.B - 1;
+    const int T = a.T;
+
+    Team<real, NX, NU> tm;
+    tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
+    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
+    const real *gf = a.factor + (size_t)b * T * C::XT;
+    const real *gg = a.gbar + (size_t)b * T * N;
+    for (int e = li; e < T * C::XT; e += G) tm.Xp[e] = gf[e];
+    for (int e = li; e < T * N; e += G) tm.ds[e] = -gg[e];
+    tm.rho = a.rho[b];
+    wave_sync();
+    tm.forward_solve_only();
+    tm.backward_sweep();
+    if (active) {
+        const real *zf = a.z_final + (size_t)b * T * N;
+        real *qg = a.q_grad + (size_t)b * T * N;
+        real *Qg = a.Qd_grad + (size_t)b * T * N;
+        for (int e = li; e < T * N; e += G) {
+            real w = tm.ds[e];
+            qg[e] = w;
+            Qg[e] = w * zf[e];
+        }
+    }
+}
+
+template <typename real, int NX, int NU>
+size_t lds_bytes_for(int T) {
+    using C = Cfg<real, NX, NU>;
+    return (size_t)C::QPW * C::team_words(T) * sizeof(real);
+}
+
+// Launches `fn` with one wavefront per workgroup and the team LDS image as dynamic LDS.
+template <typename real, int NX, int NU, typename Fn, typename... Args>
+int launch_team_kernel(Fn fn, int B, int T, hipStream_t stream, Args... args) {
+    using C = Cfg<real, NX, NU>;
+    const size_t lds = lds_bytes_for<real, NX, NU>(T);
+    if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    const unsigned grid = (unsigned)((B + C::QPW - 1) / C::QPW);
+    if (lds > 48 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return ALQP_E_LAUNCH;
+    }
+    return launch_maybe_coop(fn, grid, lds, stream, args...);
+}
+
+inline long team_simds() {   // SIMDs of the device (4 per CU)
+    static long n = 0;
+    if (n == 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+        n = 4L * cus;
+    }
+    return n;
+}
+
+template <typename real>
+int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
+        if constexpr (sizeof(real) == 4) {   // only fp32 has a capped build, for more than one wavefront per SIMD
+            const long waves = (a.B + Cfg<real, NX, NU>::QPW - 1) / Cfg<real, NX, NU>::QPW;
+            if (waves > team_simds())
+                return launch_team_kernel<real, NX, NU>(k_solve_lin<real, NX, NU, false, 2>, a.B, a.T, stream, a, TraceArgs<real>{});
+        }
+        return launch_team_kernel<real, NX, NU>(k_solve_lin<real, NX, NU, false, 1>, a.B, a.T, stream, a, TraceArgs<real>{});
+    });
+}
+
+template <typename real>
+int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        return launch_team_kernel<real, NX, NU>(k_newton_step<real, NX, NU>, a.B, a.T, stream, a);
+    });
+}
+
+template <typename real>
+int dispatch_backward(int nx, int nu, const BwdArgs<real> &a, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        return launch_team_kernel<real, NX, NU>(k_backward<real, NX, NU>, a.B, a.T, stream, a);
+    });
+}
+
+template <typename real>
+size_t lds_query(int nx, int nu, int T) {
+    return for_dims(nx, nu, size_t(0), [&](auto NX, auto NU) { return lds_bytes_for<real, NX, NU>(T); });
+}
+
+template int dispatch_solve<float>(int, int, const SolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
+template int dispatch_solve<double>(int, int, const SolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+template int dispatch_step<float>(int, int, const StepArgs<float> &, hipStream_t);
+template int dispatch_step<double>(int, int, const StepArgs<double> &, hipStream_t);
+template int dispatch_backward<float>(int, int, const BwdArgs<float> &, hipStream_t);
+template int dispatch_backward<double>(int, int, const BwdArgs<double> &, hipStream_t);
+template size_t lds_query<float>(int, int, int);
+template size_t lds_query<double>(int, int, int);
+
+}  // namespace alqp
+
+#ifdef ALQP_PHASE_TIMING
+// debug build only: read (and optionally reset) the per-phase cycle counters of k_solve_lin (team kernel)
+extern "C" int alqp_debug_team_cycles(unsigned long long *out8, int reset) {
+    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(alqp::g_team_cycles), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[8] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(alqp::g_team_cycles), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif

@@ -1,8 +1,11 @@
 #!/bin/bash
-# Builds libmi_alqp.so for gfx950 (MI355X). hipcc cross-compiles without a GPU.
-# alqp_kernels.hip is compiled as three objects in parallel (team+ABI, quad fp32, quad fp64),
-# alqp_ipm.hip (interior-point path, generic kernel + ABI) as a fourth, alqp_ipm_g4.hip (its register-resident kernel)
-# once per dtype.
+# Builds libmi_alqp.so for gfx950 (MI355X). hipcc cross-compiles without a GPU. One translation unit per kernel family,
+# all compiled in parallel; arguments go to every compile.
+#   ALQP_ONLY="obj ..."   recompile only these objects of the list below and relink (the others must exist from a full
+#                         build), e.g. ALQP_ONLY="alqp_ipm_g4_f64 alqp_ipm_g4_f32" ./build.sh
+#   ALQP_OBJ_SUFFIX=_x    with ALQP_ONLY: write those objects as build/<obj>_x.o, so that a debug compile leaves the
+#                         product objects alone
+#   ALQP_OUT=path         the library to link (default libmi_alqp.so)
 set -euo pipefail
 cd "$(dirname "$0")"
 # -pragma-unroll-threshold: the panel loops of alqp_quad.hpp must be fully unrolled (register
@@ -11,21 +14,35 @@ cd "$(dirname "$0")"
 # add instructions (A/B on one box: headline fp32 quad kernel 5.165 -> 5.269 M solves/s, resident interior-point fp64
 # 372 k -> 382 k QP/s; nothing measured got slower)
 FLAGS="--offload-arch=gfx950 -O2 -std=c++17 -fPIC -I../../include -mllvm -pragma-unroll-threshold=1000000"
+# object, source, defines of that object: what libmi_alqp.so is made of
+UNITS="
+alqp_abi         alqp_abi.hip
+alqp_team        alqp_team.hip
+alqp_aux         alqp_aux.hip
+alqp_quad_f32    alqp_quad.hip        -DALQP_QUAD_F32
+alqp_quad_f64    alqp_quad.hip        -DALQP_QUAD_F64
+alqp_dyn_casadi  alqp_dyn_casadi.hip
+alqp_ipm         alqp_ipm.hip
+alqp_ipm_g4_f64  alqp_ipm_g4.hip      -DALQP_G4_F64
+alqp_ipm_g4_f32  alqp_ipm_g4.hip      -DALQP_G4_F32
+alqp_dyn_rigid   alqp_dyn_rigid.hip
+"
+ONLY="${ALQP_ONLY:-}"
+for name in $ONLY; do
+  grep -q "^$name " <<< "$UNITS" || { echo "build.sh: ALQP_ONLY names no object of the library: $name" >&2; exit 2; }
+done
 mkdir -p build
 pids=()
-for part in 1 2 3; do
-  hipcc $FLAGS -DALQP_PART=$part -c alqp_kernels.hip -o build/alqp_part$part.o "$@" &
-  pids+=($!)
-done
-hipcc $FLAGS -c alqp_ipm.hip -o build/alqp_ipm.o "$@" &
-pids+=($!)
-# register/LDS-resident interior-point kernel: one object per dtype
-hipcc $FLAGS -DALQP_G4_F64 -c alqp_ipm_g4.hip -o build/alqp_ipm_g4_f64.o "$@" &
-pids+=($!)
-hipcc $FLAGS -DALQP_G4_F32 -c alqp_ipm_g4.hip -o build/alqp_ipm_g4_f32.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c alqp_dyn_rigid.hip -o build/alqp_dyn_rigid.o "$@" &   # quadrotor / flying-cartpole dynamics providers
-pids+=($!)
+objs=()
+while read -r obj src defs; do
+  [ -n "$obj" ] || continue
+  o=build/$obj.o
+  if [ -z "$ONLY" ] || [[ " $ONLY " == *" $obj "* ]]; then
+    [ -z "$ONLY" ] || o=build/$obj${ALQP_OBJ_SUFFIX:-}.o
+    hipcc $FLAGS $defs -c "$src" -o "$o" "$@" &
+    pids+=($!)
+  fi
+  objs+=("$o")
+done <<< "$UNITS"
 for p in "${pids[@]}"; do wait "$p"; done
-hipcc --offload-arch=gfx950 -shared -fPIC build/alqp_part1.o build/alqp_part2.o build/alqp_part3.o build/alqp_ipm.o \
-  build/alqp_ipm_g4_f64.o build/alqp_ipm_g4_f32.o build/alqp_dyn_rigid.o -o libmi_alqp.so
+hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "${ALQP_OUT:-libmi_alqp.so}"

@@ -572,7 +572,7 @@ class MPC(Module):
         dims = (B, T, nx, nu)
         if not be.supported(B, T, nx, nu, dt):
             raise RuntimeError(f"mi_alqp: no kernel instance for (nx={nx}, nu={nu}, T={T}, {dt}); "
-                               "add it to ALQP_FOR_EACH_DIMS in csrc/alqp_kernels.hip")
+                               "add it to ALQP_FOR_EACH_DIMS in csrc/alqp_dims.hpp")
         bnd = self._bounds(B, dt, dev)
         lo, hi, sb, stt = bnd
         if self.state_estimator:

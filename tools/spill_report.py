@@ -2,18 +2,14 @@
 """Lists the kernels of one translation unit that spill vector registers, and flags the pattern that corrupted a test in
 round 3: a spill store immediately in front of the `s_or_b64 exec` that opens a divergent region's exit block (the store
 then runs under the region's EXEC mask - possibly 0 - and loses lanes).
-    python tools/spill_report.py [part 1|2|3] [extra hipcc flags...]"""
-import os, re, subprocess, sys, tempfile
+    python tools/spill_report.py [unit, default alqp_team.hip] [extra hipcc flags, e.g. -DALQP_QUAD_F64 for alqp_quad.hip...]"""
+import os, re, sys
+
+from kernel_digest import device_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "deq-mpc-corl_amd", "csrc")
-part = sys.argv[1] if len(sys.argv) > 1 else "1"
-out = os.path.join(tempfile.gettempdir(), f"alqp_part{part}.s")
-cmd = ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-mllvm",
-       "-pragma-unroll-threshold=1000000", f"-DALQP_PART={part}", "-S", "--cuda-device-only",
-       os.path.join(CSRC, "alqp_kernels.hip"), "-o", out] + sys.argv[2:]
-subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-txt = open(out).read()
+unit = sys.argv[1] if len(sys.argv) > 1 else "alqp_team.hip"
+txt = device_asm(os.path.join(ROOT, "deq-mpc-corl_amd", "csrc", unit), sys.argv[2:])
 lines = txt.split("\n")
 cur, hits = None, {}
 for i, l in enumerate(lines):
