@@ -63,7 +63,83 @@ class _SolveState:
     """Everything the solve needs that autograd must not see."""
 
     __slots__ = ("mpc", "x0", "z", "lam", "rho", "dx", "dx_jac", "lin", "stream_mode",
-                 "status_flag", "per_instance_status", "newton_per_al")
+                 "status_flag", "newton_per_al")
+
+
+class _Launcher:
+    """One solve's backend launches. The arguments every launch of the solve repeats are bound here once, so a call
+    site states only what differs (al_iter, max_newton, flags, skip, newton_counts, workspace / variant). Also here:
+    the backend's capabilities, each probed once with one default, and the scratch the launches share."""
+
+    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once):
+        self.be, self.st, self.dims, self.Qd, self.q, self.F, self.c = be, st, dims, Qd, q, F, c
+        self.linearize_once = linearize_once   # F, c are the linearisation frozen at the warm start
+        self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
+        self.has_backward_ws = hasattr(be, "backward_ws")
+        self.has_solve_nonlin = hasattr(be, "solve_nonlin")
+        self.can_exit_in_kernel = getattr(be, "supports_exit_in_kernel", False)
+        self.quad_min_batch = getattr(be, "QUAD_MIN_BATCH", 0)   # batch from which the quad kernels are the default
+        B, dt, dev = dims[0], st.z.dtype, st.z.device
+        # phi, rn2 and info out of ONE zeroed allocation (one fill kernel instead of three)
+        esz = torch.empty((), dtype=dt).element_size()
+        zb = torch.zeros(B * (2 * esz + 4), dtype=torch.uint8, device=dev)
+        self.phi, self.rn2 = zb[:B * esz].view(dt), zb[B * esz:2 * B * esz].view(dt)
+        self.info = zb[2 * B * esz:].view(torch.int32)
+        self.status = torch.ones(B, dtype=torch.uint8, device=dev)
+        self._x0_bounds = (st.x0, *bnd)   # x0, lo, hi, sb, stt
+        self._problem = (st.x0, st.lam, st.rho, Qd, q, *bnd)
+        self._out = dict(rnorm2=self.rn2, status=self.status, rho_scale=RHO_SCALE)
+        # set by _run when a backward pass may follow: the private quad workspace (it IS the saved factor then) with
+        # the arguments that select it, or the packed factor with ALQP_SAVE_FACTOR; nlws: the fused routes' workspace
+        self.qws, self.private_kw, self.factor, self.save_flag, self.nlws = None, {}, None, 0, None
+        self.d = self.k = self.acc = None   # Newton direction and line-search outputs of the PyTorch-dynamics steps
+        self.primed = None                  # see lin_tracked
+        self._cached = None
+
+    def lin(self, info=True, **kw):
+        st = self.st
+        return self.be.solve_lin(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, st.z, st.lam, st.rho,
+                                 self.phi, info=self.info if info else None, n_ls=N_LS, **self._out, **kw)
+
+    def lin_tracked(self, flags, private=True, **kw):
+        """solve_lin with the ALQP_WS_PRIMED bookkeeping. `primed` is the workspace whose records hold THIS solve's
+        current z / lam (written by the previous quad launch), else None: a launch on that workspace that saves no
+        factor skips its copy-in pass. The launch goes to the solve's private workspace if it has one (and `private`),
+        else to the cached scratch a quad launch will use. False: a refused cooperative launch, nothing done.
+        The cached scratch is fetched once per solve: the backend hands out the same tensor for the same dims and
+        dtype, and nothing between this solve's launches (dx / dx_jac included) may make it grow its cache."""
+        on = self.private_kw if private else {}
+        wsx = on.get("workspace")
+        if wsx is None and self.cached_ws is not None:
+            if self._cached is None:
+                self._cached = self.cached_ws(self.dims, self.st.z)[0]
+            wsx = self._cached
+        if wsx is not None and self.primed is wsx and not flags & _abi.ALQP_SAVE_FACTOR:
+            flags |= _abi.ALQP_WS_PRIMED
+        ok = self.lin(flags=flags, **on, **kw)
+        if ok is not False:
+            self.primed = wsx if getattr(self.be, "last_variant", None) == "quad" else None
+        return ok
+
+    def nonlin(self, info=True, **kw):
+        st = self.st
+        return self.be.solve_nonlin(self.dims, st.dx.fused_id, st.dx.dt, self.Qd, self.q, *self._x0_bounds, st.z, st.lam,
+                                    st.rho, self.phi, info=self.info if info else None, workspace=self.nlws,
+                                    **self._out, **kw)
+
+    def merit(self, z, xn, **okw):
+        self.be.merit(self.dims, 1, z, xn, *self._problem, self.phi, self.rn2, **okw)
+
+    def newton_step(self, z, xn, F, **kw):
+        self.be.newton_step(self.dims, z, xn, F, *self._problem, self.d, **kw)
+
+    def merit_pick(self, xn_all, z, **okw):
+        self.be.merit_pick(self.dims, N_LS, self.d, xn_all, *self._problem, z, self.phi, rnorm2=self.rn2,
+                           k_out=self.k, accept_out=self.acc, **okw)
+
+    def dual_update(self, xn, **okw):
+        st = self.st
+        self.be.dual_update(self.dims, st.z, xn, *self._x0_bounds, st.lam, st.rho, RHO_SCALE, **okw)
 
 
 class _ALSolve(torch.autograd.Function):
@@ -313,8 +389,7 @@ class MPC(Module):
 
     def _has_extra_rows(self):
         """True when the constraint-row set differs from the plain MPC's (obstacle rows, state estimator): a predicate
-        that moves no tensor (the former `bool(_obs_kwargs(dtype, "cpu"))` copied the obstacle centres to the host and
-        synchronised on every solve)."""
+        that moves no tensor (`_obs_kwargs` would copy the obstacle centres and synchronise on every solve)."""
         return bool(self.state_estimator)
 
     def _as_lindx(self, dx, B):
@@ -369,9 +444,7 @@ class MPC(Module):
         """sum_b sum_rows r+^2 as a 1-element float64 device tensor (all-reduced over the ranks
         of a sharded batch); nothing is synchronised with the host."""
         s = self._exit_terms(rn2, info).sum(dtype=torch.float64).reshape(1)
-        if self.process_group is not None or (
-                torch.distributed.is_available() and torch.distributed.is_initialized()
-                and getattr(self, "sync_global_exit", False)):
+        if self._sharded():
             torch.distributed.all_reduce(s, group=self.process_group)
         return s
 
@@ -381,9 +454,7 @@ class MPC(Module):
         partial sums are all-reduced (8 bytes over RCCL) so that every rank takes the
         same decision the un-sharded reference would."""
         s = self._exit_terms(rn2, info).sum(dtype=torch.float64)
-        if self.process_group is not None or (
-                torch.distributed.is_available() and torch.distributed.is_initialized()
-                and getattr(self, "sync_global_exit", False)):
+        if self._sharded():
             torch.distributed.all_reduce(s, group=self.process_group)
         return math.sqrt(float(s.item()))
 
@@ -436,67 +507,6 @@ class MPC(Module):
         nx = self.n_state
         return z[..., :nx].float(), z[..., nx:].float(), st.status_flag
 
-    # one NewtonAL.forward worth of work on affine data, host-driven exit
-    def _newton_al_lin(self, st, Qd, q, F, c, bnd, ws, need_factor):
-        be = self.backend
-        dims = (st.z.shape[0], self.T, self.n_state, self.n_ctrl)
-        lo, hi, sb, stt = bnd
-        common = dict(rnorm2=ws["rn2"], info=ws["info"], status=ws["status"], n_ls=N_LS,
-                      rho_scale=RHO_SCALE)
-        if ws.get("qws") is not None:   # quad solve on a private workspace: it IS the saved factor
-            common["workspace"] = ws["qws"]
-            common["variant"] = "quad"
-            need_factor = False
-        fl_save = _abi.ALQP_SAVE_FACTOR if need_factor else 0
-        wsx = common.get("workspace")
-        if wsx is None and hasattr(be, "_workspace"):
-            wsx = be._workspace(dims, st.z)[0]   # the cached scratch a quad launch will use
-        # ALQP_WS_PRIMED bookkeeping: ws["primed"] is the workspace whose records hold THIS
-        # solve's current z/lam (written by the previous quad launch), else None
-        def pflag():
-            return _abi.ALQP_WS_PRIMED if (wsx is not None and ws.get("primed") is wsx) else 0
-        def after():
-            ws["primed"] = wsx if getattr(be, "last_variant", None) == "quad" else None
-        if self.exit_mode == "fixed":
-            be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"],
-                         factor=ws.get("factor"), al_iter=1, max_newton=MAX_NEWTON,
-                         flags=_abi.ALQP_INIT_MERIT | fl_save | (0 if fl_save else pflag()), **common)
-            after()
-            return MAX_NEWTON
-        be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"],
-                     al_iter=1, max_newton=0, flags=_abi.ALQP_INIT_MERIT | pflag(), **common)
-        after()
-        # The reference's batch-global exit test (al_utils.py:551-564) is taken on the device: all
-        # MAX_NEWTON launches are enqueued, each one a no-op once ctl[0] is set, and the number of
-        # executed steps (ctl[1]) is read back once per solve. No host round trip per Newton step.
-        ctl = torch.zeros(3, dtype=torch.float64, device=st.z.device)
-        be.exit_test(self._global_sumsq(ws["rn2"], ws["info"]), ctl, 0)
-        for _ in range(MAX_NEWTON):
-            # same workspace as the launch before, nothing touched in between: no copy-in pass
-            be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"],
-                         factor=ws.get("factor"), al_iter=1, max_newton=1,
-                         flags=fl_save | (0 if fl_save else pflag()), skip=ctl, **common)
-            after()
-            be.exit_test(self._global_sumsq(ws["rn2"], ws["info"]), ctl, 1)
-        return ctl
-
-    def _newton_al_fused_nl(self, st, Qd, q, bnd, ws):
-        """NewtonAL.forward for a dynamics model compiled into the library, reference exit rule:
-        alqp_solve_nonlin once per Newton step, alqp_exit_test in between (no host round trip)."""
-        be = self.backend
-        dims = (st.z.shape[0], self.T, self.n_state, self.n_ctrl)
-        lo, hi, sb, stt = bnd
-        common = dict(rnorm2=ws["rn2"], info=ws["info"], status=ws["status"], rho_scale=RHO_SCALE,
-                      workspace=ws.get("nlws"))
-        args = (dims, st.dx.fused_id, st.dx.dt, Qd, q, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"])
-        be.solve_nonlin(*args, al_iter=1, max_newton=0, flags=_abi.ALQP_INIT_MERIT, **common)
-        ctl = torch.zeros(3, dtype=torch.float64, device=st.z.device)
-        be.exit_test(self._global_sumsq(ws["rn2"], ws["info"]), ctl, 0)
-        for _ in range(MAX_NEWTON):
-            be.solve_nonlin(*args, al_iter=1, max_newton=1, flags=0, skip=ctl, **common)
-            be.exit_test(self._global_sumsq(ws["rn2"], ws["info"]), ctl, 1)
-        return ctl
-
     def _linearize(self, st, z):
         """dx_jac at every (x_t, u_t), t < T-1 -> (f(z) [B,T-1,nx], F = [A|B] [B,T-1,nx,n]).
         Called the way the reference does (al_utils.py:501-503, 233-248): grad mode on and the
@@ -512,69 +522,186 @@ class MPC(Module):
         F = torch.cat((A.detach().reshape(B, T - 1, nx, nx), Bm), dim=-1).to(z.dtype).contiguous()
         return xn_j.detach().reshape(B, T - 1, nx).to(z.dtype).contiguous(), F
 
-    def _newton_al_nonlin(self, st, Qd, q, bnd, ws, need_factor):
-        """NewtonAL.forward (al_utils.py:451-576) with `dx`/`dx_jac` as PyTorch calls
-        between kernel launches."""
-        be = self.backend
-        B, T, nx, nu = st.z.shape[0], self.T, self.n_state, self.n_ctrl
-        n = nx + nu
-        dims = (B, T, nx, nu)
-        lo, hi, sb, stt = bnd
-        z = st.z
-        dt = z.dtype
+    def _true_next(self, st, zz):
+        """f(x_t, u_t) of the TRUE dynamics, PyTorch-coded: zz [..., T, n] -> [..., T-1, nx]."""
+        nx = self.n_state
+        xn = st.dx(zz[..., :-1, :nx].reshape(-1, nx), zz[..., :-1, nx:].reshape(-1, self.n_ctrl))
+        return xn.reshape(*zz.shape[:-2], self.T - 1, nx).to(zz.dtype).contiguous()
 
-        def dyn(zz):  # zz [..., T, n] -> f(x_t,u_t) [..., T-1, nx]
-            lead = zz.shape[:-2]
-            xn = st.dx(zz[..., :-1, :nx].reshape(-1, nx), zz[..., :-1, nx:].reshape(-1, nu))
-            return xn.reshape(*lead, T - 1, nx).to(dt).contiguous()
+    def _fused_model(self, st):
+        """True when the dynamics model is compiled into the library (dynamics.py) and this solve may take it: plain
+        row set, one call per solve (not the stream loop), the sizes it was compiled for, and the model's default
+        route unless `prefer_fused`."""
+        dx = st.dx
+        return (st.lin is None and not st.stream_mode and not self._has_extra_rows()
+                and getattr(dx, "fused_id", None) is not None
+                and (getattr(dx, "fused_default", True) or self.prefer_fused)
+                and (getattr(dx, "nx", None), getattr(dx, "nu", None)) == (self.n_state, self.n_ctrl))
 
-        okw = self._obs_kwargs(dt, z.device)   # {} or {"obs": (centres, radius)} (Obstacle_MPC)
-        xn = dyn(z)
-        be.merit(dims, 1, z, xn, st.x0, st.lam, st.rho, Qd, q, lo, hi, sb, stt, ws["phi"], ws["rn2"], **okw)
-        old = self._global_norm(ws["rn2"], ws["info"]) if self.exit_mode == "reference" else None
-        alphas = (2.0 ** -torch.arange(N_LS, device=z.device, dtype=dt)).view(N_LS, 1, 1, 1)
+    # ---- the Newton loop of one AL iteration (NewtonAL.forward, al_utils.py:451-576), per route ----
+    def _newton_device_exit(self, L, launch, **step_kw):
+        """Reference exit rule without a host round trip per Newton step: the batch-global test
+        (al_utils.py:551-564) is taken on the device. All MAX_NEWTON one-step launches are enqueued, each one a
+        no-op once ctl[0] is set, and the number of executed steps (ctl[1]) is read back once per solve."""
+        launch(al_iter=1, max_newton=0, flags=_abi.ALQP_INIT_MERIT)
+        ctl = torch.zeros(3, dtype=torch.float64, device=L.st.z.device)
+        L.be.exit_test(self._global_sumsq(L.rn2, L.info), ctl, 0)
+        for _ in range(MAX_NEWTON):
+            launch(al_iter=1, max_newton=1, skip=ctl, **step_kw)
+            L.be.exit_test(self._global_sumsq(L.rn2, L.info), ctl, 1)
+        return ctl[1]
+
+    def _newton_lin(self, L):
+        """Affine data: every launch on the same workspace as the one before with nothing touched in between, so
+        none but the first pays a copy-in pass (L.lin_tracked)."""
+        if self.exit_mode == "fixed":
+            L.lin_tracked(al_iter=1, max_newton=MAX_NEWTON, flags=_abi.ALQP_INIT_MERIT | L.save_flag, factor=L.factor)
+            return MAX_NEWTON
+        return self._newton_device_exit(L, L.lin_tracked, flags=L.save_flag, factor=L.factor)
+
+    def _newton_torch(self, L):
+        """`dx` / `dx_jac` as PyTorch calls between kernel launches. Returns (steps, F of the last one)."""
+        st, z = L.st, L.st.z
+        okw = self._obs_kwargs(z.dtype, z.device)   # {} or {"obs": (centres, radius)} (Obstacle_MPC)
+        L.merit(z, self._true_next(st, z), **okw)
+        old = self._global_norm(L.rn2, L.info) if self.exit_mode == "reference" else None
+        alphas = (2.0 ** -torch.arange(N_LS, device=z.device, dtype=z.dtype)).view(N_LS, 1, 1, 1)
+        # from B = QUAD_MIN_BATCH on the direction comes from the quad kernels (obstacle rows / the state-estimator
+        # row set included), whose factor stays in the workspace records: the private one when backward follows
+        qws = L.qws   # (fetched once per solve, on the assumption L.lin_tracked states)
+        if qws is None and L.cached_ws is not None and L.dims[0] >= L.quad_min_batch:
+            qws = L.cached_ws(L.dims, z)[0]
         steps = 0
         while steps < MAX_NEWTON:
             steps += 1
             xn, F = self._linearize(st, z)
-            # from B = QUAD_MIN_BATCH on the direction comes from the quad kernels,
-            # whose factor stays in the workspace records: a private one (ws["qws"]) when backward follows
-            qws = ws.get("qws")
-            if qws is None and hasattr(be, "_workspace") and B >= getattr(be, "QUAD_MIN_BATCH", 1 << 62):
-                qws = be._workspace(dims, z)[0]
-            if qws is not None:   # (obstacle rows / the state-estimator row set included: alqp_newton_step_ws_obs)
-                be.newton_step(dims, z, xn, F, st.x0, st.lam, st.rho, Qd, q, lo, hi, sb, stt, ws["d"],
-                               info=ws["info"], workspace=qws, **okw)
-            else:
-                be.newton_step(dims, z, xn, F, st.x0, st.lam, st.rho, Qd, q, lo, hi, sb, stt, ws["d"],
-                               factor=ws.get("factor") if need_factor else None, info=ws["info"], **okw)
-            if need_factor:
-                ws["F_last"] = F
-            zc = (z.unsqueeze(0) + alphas * ws["d"].unsqueeze(0)).contiguous()
-            xnc = dyn(zc)
+            L.newton_step(z, xn, F, info=L.info, **(dict(workspace=qws) if qws is not None else dict(factor=L.factor)),
+                          **okw)
+            zc = (z.unsqueeze(0) + alphas * L.d.unsqueeze(0)).contiguous()
             # 20 merits + decision + update in one launch; rn2 <- the chosen candidate's when accepted
-            be.merit_pick(dims, N_LS, ws["d"], xnc, st.x0, st.lam, st.rho, Qd, q, lo, hi, sb, stt, z, ws["phi"],
-                          rnorm2=ws["rn2"], k_out=ws["k"], accept_out=ws["acc"], **okw)
+            L.merit_pick(self._true_next(st, zc), z, **okw)
             if self.exit_mode == "reference":
-                new = self._global_norm(ws["rn2"], ws["info"])
+                new = self._global_norm(L.rn2, L.info)
                 if new < 1e-3 or (math.isfinite(new) and abs(old - new) / new < 1e-3):   # inf: a tripped instance, no exit
                     break
                 old = new
-        return steps
+        return steps, F
+
+    # ---- one AL iteration (Newton loop + dual update), per route: -> (Newton steps, F of the last one) ----
+    # (one signature for all four, so that _solve_al_loop can pick the body once: only the fused one reads need_grad)
+    def _al_iter_fused(self, L, need_grad):
+        """Compiled-in model, reference exit: one launch per Newton step (the model inlined), the batch-global exit
+        test on the device, then the dual update launch."""
+        if need_grad and L.nlws is None:
+            L.nlws = L.be.new_workspace_nonlin(L.dims, L.st.z)
+        steps = self._newton_device_exit(L, L.nonlin, flags=0)
+        L.nonlin(al_iter=1, max_newton=0, flags=_abi.ALQP_DUAL_UPDATE, info=False)
+        # L and F of the last executed Newton step are still in the workspace
+        return steps, (L.be.nonlin_F_view(L.nlws, L.dims) if need_grad else None)
+
+    def _al_iter_coop(self, L, need_grad):
+        """Affine data, reference exit: starting merit, Newton loop with the batch-global exit and dual update in one
+        cooperative launch. None (nothing launched) when the grid cannot be co-resident."""
+        cnt = torch.zeros(1, dtype=torch.int32, device=L.st.z.device)
+        if not L.lin_tracked(al_iter=1, max_newton=MAX_NEWTON, factor=L.factor, newton_counts=cnt,
+                             flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE | L.save_flag):
+            return None
+        return cnt[0], L.F
+
+    def _al_iter_lin(self, L, need_grad):
+        """Affine data (given, or the frozen linearisation of `linearize_once`), a launch per Newton step."""
+        steps = self._newton_lin(L)
+        if L.linearize_once:
+            self._dual_update_torch(L)
+        else:
+            # never on the private workspace: keep the saved factor's workspace out of later launches altogether
+            L.lin_tracked(al_iter=1, max_newton=0, flags=_abi.ALQP_DUAL_UPDATE, private=False, info=False)
+        return steps, L.F
+
+    def _al_iter_torch(self, L, need_grad):
+        out = self._newton_torch(L)
+        self._dual_update_torch(L)
+        return out
+
+    def _dual_update_torch(self, L):
+        """Dual update with the TRUE dynamics (AL_mpc.py:315-317 / :397-399)."""
+        st = L.st
+        xn = self._true_next(st, st.z)
+        okw = self._obs_kwargs(st.z.dtype, st.z.device)
+        L.merit(st.z, xn, **okw)
+        L.dual_update(xn, **okw)
+        L.primed = None   # lam/rho changed behind the workspace records' back
+
+    # ---- the routes of a solve: each -> (newton_per_al, rho_last, F_last) ----
+    def _solve_lin_one_launch(self, L, need_grad, coop):
+        """Affine dynamics, the whole solve in ONE launch: 4 Newton steps per AL iteration (fixed exit), or with `coop`
+        the reference's batch-global exit test taken INSIDE one cooperative launch (grid-wide barrier + ordered sum
+        per Newton step, ALQP_EXIT_IN_KERNEL). None when that launch was refused."""
+        counts = torch.zeros(self.al_iter, dtype=torch.int32, device=L.st.z.device) if coop else None
+        ok = L.lin(al_iter=self.al_iter, max_newton=MAX_NEWTON, factor=L.factor, **L.private_kw,
+                   flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE | L.save_flag,
+                   **(dict(newton_counts=counts) if coop else {}))
+        if coop and not ok:
+            return None
+        npa = list(counts.unbind()) if coop else [MAX_NEWTON] * self.al_iter
+        return npa, (L.st.rho / RHO_SCALE if need_grad or coop else None), L.F
+
+    def _solve_fused_one_launch(self, L, need_grad, coop):
+        """Dynamics model compiled into the library: the whole nonlinear solve in ONE launch, no PyTorch round trip
+        between Newton steps; `coop` and None as in _solve_lin_one_launch."""
+        if need_grad:   # private workspace: its records and F region are the saved factor
+            L.nlws = L.be.new_workspace_nonlin(L.dims, L.st.z)
+        counts = torch.zeros(self.al_iter, dtype=torch.int32, device=L.st.z.device) if coop else None
+        ok = L.nonlin(al_iter=self.al_iter, max_newton=MAX_NEWTON, flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE,
+                      **(dict(newton_counts=counts) if coop else {}))
+        if coop and not ok:
+            return None
+        npa = list(counts.unbind()) if coop else [MAX_NEWTON] * self.al_iter
+        return npa, L.st.rho / RHO_SCALE, (L.be.nonlin_F_view(L.nlws, L.dims) if need_grad else None)
+
+    def _solve_al_loop(self, L, need_grad, fused, coop):
+        """The AL outer loop on the host (AL_mpc.py:260-339 / :342-423), one of four bodies per iteration."""
+        st, stream = L.st, L.st.stream_mode
+        prev_mean = None
+        if L.linearize_once:  # dyn_res_clamp_prev starts at the residual of the warm start (:358-369)
+            L.merit(st.z, self._true_next(st, st.z))
+            prev_mean = self._global_mean(L.rn2.sqrt())
+        body = (self._al_iter_fused if fused else self._al_iter_coop if coop
+                else self._al_iter_lin if L.F is not None else self._al_iter_torch)
+        npa, rho_last, F_last = [], None, None
+        for _ in range(100 if L.linearize_once else self.al_iter):
+            rho_last = st.rho.clone()
+            out = body(L, need_grad)
+            if out is None:   # cooperative launch refused: a launch per Newton step from here on, no second try
+                body = self._al_iter_lin
+                out = body(L, need_grad)
+            npa.append(out[0])
+            F_last = out[1]
+            if stream:
+                if L.linearize_once:
+                    mean = self._global_mean(L.rn2.sqrt())
+                    if prev_mean is not None and not mean < prev_mean:
+                        break
+                    prev_mean = mean
+                if self._global_max(st.rho) > self.rho_max:
+                    break
+        if stream and self._global_max(st.rho) > self.rho_max:
+            st.status_flag = True
+        return npa, rho_last, F_last
 
     def _run(self, st, Qd, q, need_grad):
-        """The AL outer loop (AL_mpc.py:260-339 / :342-423). Mutates st.z/lam/rho.
-        Returns (factor, F_last, rho_last) when a backward pass may follow."""
+        """One solve: the checks that raise, the allocation, then the route - the one-launch route that applies,
+        else the AL loop. Mutates st.z/lam/rho. Returns (kind, factor, F_last, rho_last) when a backward pass may
+        follow."""
         be = self.backend
         B, T, nx, nu = st.z.shape[0], self.T, self.n_state, self.n_ctrl
         n = nx + nu
         dt, dev = st.z.dtype, st.z.device
         dims = (B, T, nx, nu)
+        stream = st.stream_mode
         if not be.supported(B, T, nx, nu, dt):
             raise RuntimeError(f"mi_alqp: no kernel instance for (nx={nx}, nu={nu}, T={T}, {dt}); "
                                "add it to ALQP_FOR_EACH_DIMS in csrc/alqp_dims.hpp")
-        bnd = self._bounds(B, dt, dev)
-        lo, hi, sb, stt = bnd
         if self.state_estimator:
             # cost gradient on the states only (al_utils_se.py:300-310) while the Hessian keeps diag(Q) on the
             # controls (:66-68): the kernels' `state_estimator` flag. Their merit still counts the controls' cost
@@ -582,234 +709,80 @@ class MPC(Module):
             if torch.is_tensor(getattr(st.dx, "F", None)) or self.linearize_once:
                 raise NotImplementedError("state_estimator: only the callable dx / dx_jac route exists "
                                           "(al_utils_se.py has no LinDx or frozen-linearisation branch)")
-        # phi, rn2 and info out of ONE zeroed allocation (one fill kernel instead of three)
-        esz = torch.empty((), dtype=dt).element_size()
-        zb = torch.zeros(B * (2 * esz + 4), dtype=torch.uint8, device=dev)
-        ws = {"phi": zb[:B * esz].view(dt), "rn2": zb[B * esz:2 * B * esz].view(dt),
-              "info": zb[2 * B * esz:].view(torch.int32),
-              "status": torch.ones(B, dtype=torch.uint8, device=dev)}
-        lin = st.lin
-        if need_grad and self.linearize_once and st.stream_mode:
+        if need_grad and self.linearize_once and stream:
             # al_utils_lin.NewtonAL.backward returns 14 gradients for 15 inputs (al_utils_lin.py:444-459):
             # autograd rejects it, so the reference cannot differentiate this route. Same error type.
             raise RuntimeError("MPC: the linearize_once streaming route is not differentiable (the reference's "
                                "al_utils_lin.NewtonAL.backward returns an incorrect number of gradients)")
-        has_obs = self._has_extra_rows()
-        # (round 3: the quad step kernel takes the obstacle / state-estimator rows too, so their factor can stay in its records)
-        use_qws = need_grad and hasattr(be, "backward_ws") and B >= getattr(be, "QUAD_MIN_BATCH", 0) and not (
-            bool(self.linearize_once) and st.stream_mode)
-        if use_qws:
-            ws["qws"] = be.new_workspace(dims, st.z)
-        elif need_grad:
-            ws["factor"] = torch.empty(B, T, n * (n + 1) // 2, dtype=dt, device=dev)
-        stream = st.stream_mode
         if self.linearize_once and not stream:
             # The reference cannot run this combination either: al_solve (AL_mpc.py:292-306) hands the
             # frozen-linearisation dict to al_utils.merit_grad_hessian, which calls it
             # ("TypeError: 'dict' object is not callable", al_utils.py:237). Same error type here.
             raise TypeError("MPC: linearize_once is only defined for the streaming route (after "
                             "warm_start_initialize); the reference's al_solve raises TypeError on it as well")
-        linearize_once = bool(self.linearize_once) and stream
-        if has_obs and linearize_once:
+        linearize_once = bool(self.linearize_once)
+        if self._has_extra_rows() and linearize_once:
             raise NotImplementedError("Obstacle_MPC with linearize_once: the reference's frozen-linearisation "
                                       "module knows no obstacle rows (AL_mpc_custom.py:68, 75, 83)")
-        npa = []
-        rho_last = None
-        F_last = None
-
-        if lin is None or linearize_once:
-            ws.update(d=torch.empty(B, T, n, dtype=dt, device=dev),
-                      phis=torch.empty(N_LS, B, dtype=dt, device=dev),
-                      rn2s=torch.empty(N_LS, B, dtype=dt, device=dev),
-                      k=torch.zeros(B, dtype=torch.int32, device=dev),
-                      acc=torch.zeros(B, dtype=torch.int32, device=dev))
-
-        def true_next(z):
-            xn = st.dx(z[:, :-1, :nx].reshape(-1, nx), z[:, :-1, nx:].reshape(-1, nu))
-            return xn.reshape(B, T - 1, nx).to(dt).contiguous()
 
         F = c = None
-        if lin is not None and not linearize_once:
-            F = lin[0].detach().to(device=dev, dtype=dt).contiguous()
-            c = lin[1].detach().to(device=dev, dtype=dt).contiguous()
-        elif linearize_once:
+        if linearize_once:
             # frozen linearisation captured once per call (al_utils_lin.py:140-169)
             # note the offset: x_{t+1} of the WARM START minus F_t z_t, not f(z_t) - F_t z_t (:154)
-            z = st.z
-            _, F = self._linearize(st, z)
-            c = (z[:, 1:, :nx] - torch.einsum("btij,btj->bti", F, z[:, :-1])).contiguous()
+            _, F = self._linearize(st, st.z)
+            c = (st.z[:, 1:, :nx] - torch.einsum("btij,btj->bti", F, st.z[:, :-1])).contiguous()
+        elif st.lin is not None:
+            F = st.lin[0].detach().to(device=dev, dtype=dt).contiguous()
+            c = st.lin[1].detach().to(device=dev, dtype=dt).contiguous()
+        L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once)
+        # the quad kernels take the obstacle / state-estimator rows too, so their factor can stay in the records
+        use_qws = need_grad and L.has_backward_ws and B >= L.quad_min_batch
+        if use_qws:
+            L.qws = be.new_workspace(dims, st.z)
+            L.private_kw = dict(workspace=L.qws, variant="quad")
+        elif need_grad:
+            L.factor = torch.empty(B, T, n * (n + 1) // 2, dtype=dt, device=dev)
+            L.save_flag = _abi.ALQP_SAVE_FACTOR
+        if st.lin is None or linearize_once:
+            L.d = torch.empty(B, T, n, dtype=dt, device=dev)
+            L.k = torch.zeros(B, dtype=torch.int32, device=dev)
+            L.acc = torch.zeros(B, dtype=torch.int32, device=dev)
 
-        # ---- reference exit rule, un-sharded batch, affine dynamics: the batch-global test of the Newton loop is taken
-        # INSIDE one cooperative launch (grid-wide barrier + ordered sum per Newton step, ALQP_EXIT_IN_KERNEL) instead
-        # of a launch per Newton step with alqp_exit_test in between. Falls through when the grid cannot be co-resident.
-        done_in_kernel = False
-        coop = (F is not None and not linearize_once and self.exit_mode == "reference" and not self._sharded()
-                and getattr(be, "supports_exit_in_kernel", False)
-                and (self.exit_in_kernel is True
-                     or (self.exit_in_kernel == "auto" and B < getattr(be, "QUAD_MIN_BATCH", 0)
-                         and -(-B // max(1, be.qps_per_wave(B, T, nx, nu, dt))) <= 512)))
-        if coop and not stream:
-            save = need_grad and not use_qws
-            flags = _abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE | (_abi.ALQP_SAVE_FACTOR if save else 0)
-            extra = dict(workspace=ws["qws"], variant="quad") if use_qws else {}
-            counts = torch.zeros(self.al_iter, dtype=torch.int32, device=dev)
-            done_in_kernel = be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"],
-                                          rnorm2=ws["rn2"], info=ws["info"], status=ws["status"],
-                                          factor=ws.get("factor"), al_iter=self.al_iter, max_newton=MAX_NEWTON,
-                                          n_ls=N_LS, flags=flags, rho_scale=RHO_SCALE, newton_counts=counts, **extra)
-            if done_in_kernel:
-                npa = list(counts.unbind())
-                rho_last = st.rho / RHO_SCALE
-                F_last = F
+        # Reference exit rule on an un-sharded batch: the batch-global test of the Newton loop may be taken inside a
+        # cooperative launch instead of between one-step launches (see `exit_in_kernel` in __init__)
+        in_kernel = self.exit_mode == "reference" and not self._sharded() and L.can_exit_in_kernel
+        auto = self.exit_in_kernel == "auto"
+        coop = (in_kernel and F is not None and not linearize_once and (self.exit_in_kernel is True or (
+            auto and B < L.quad_min_batch and -(-B // max(1, be.qps_per_wave(B, T, nx, nu, dt))) <= 512)))
+        fused = L.has_solve_nonlin and self._fused_model(st)
+        coop_nl = in_kernel and fused and (self.exit_in_kernel is True or (auto and -(-B // 16) <= 512))
+        fixed = self.exit_mode == "fixed"
+        res = None
+        if F is not None and not stream and (coop or fixed):
+            res = self._solve_lin_one_launch(L, need_grad, coop)
+        elif fused and (coop_nl or fixed):
+            res = self._solve_fused_one_launch(L, need_grad, coop_nl)
+        if res is None:
+            res = self._solve_al_loop(L, need_grad, fused, coop)
+        npa, rho_last, F_last = res
 
-        # ---- fast path: the whole solve in ONE launch -----------------------------------
-        if done_in_kernel:
-            pass
-        elif F is not None and not stream and self.exit_mode == "fixed":
-            save = need_grad and not use_qws
-            flags = _abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE | (_abi.ALQP_SAVE_FACTOR if save else 0)
-            extra = dict(workspace=ws["qws"], variant="quad") if use_qws else {}
-            be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"],
-                         rnorm2=ws["rn2"], info=ws["info"], status=ws["status"],
-                         factor=ws.get("factor"), al_iter=self.al_iter, max_newton=MAX_NEWTON,
-                         n_ls=N_LS, flags=flags, rho_scale=RHO_SCALE, **extra)
-            npa = [MAX_NEWTON] * self.al_iter
-            rho_last = st.rho / RHO_SCALE if need_grad else None
-            F_last = F
-        elif (F is None and not stream and self.exit_mode == "fixed" and not has_obs
-              and getattr(st.dx, "fused_id", None) is not None and hasattr(be, "solve_nonlin")
-              and (getattr(st.dx, "fused_default", True) or self.prefer_fused)
-              and (getattr(st.dx, "nx", None), getattr(st.dx, "nu", None)) == (nx, nu)):
-            # ---- nonlinear dynamics whose model is compiled into the library (dynamics.py): the
-            # whole nonlinear solve in ONE launch, no PyTorch round trip between Newton steps
-            if need_grad:   # private workspace: its records and F region are the saved factor
-                ws["nlws"] = be.new_workspace_nonlin(dims, st.z)
-            be.solve_nonlin(dims, st.dx.fused_id, st.dx.dt, Qd, q, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho,
-                            ws["phi"], rnorm2=ws["rn2"], info=ws["info"], status=ws["status"],
-                            al_iter=self.al_iter, max_newton=MAX_NEWTON,
-                            flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE, rho_scale=RHO_SCALE,
-                            workspace=ws.get("nlws"))
-            npa = [MAX_NEWTON] * self.al_iter
-            rho_last = st.rho / RHO_SCALE
-            if need_grad:
-                F_last = be.nonlin_F_view(ws["nlws"], dims)
-        else:
-            num_iters = 100 if linearize_once else self.al_iter
-            prev_mean = None
-            if linearize_once:  # dyn_res_clamp_prev starts at the residual of the warm start (:358-369)
-                xn = true_next(st.z)
-                be.merit(dims, 1, st.z, xn, st.x0, st.lam, st.rho, Qd, q, lo, hi, sb, stt,
-                         ws["phi"], ws["rn2"])
-                prev_mean = self._global_mean(ws["rn2"].sqrt())
-            fused_nl = (F is None and not stream and self.exit_mode == "reference" and not has_obs
-                        and getattr(st.dx, "fused_id", None) is not None and hasattr(be, "solve_nonlin")
-                        and (getattr(st.dx, "fused_default", True) or self.prefer_fused)
-                        and (getattr(st.dx, "nx", None), getattr(st.dx, "nu", None)) == (nx, nu))
-            if fused_nl and not self._sharded() and getattr(be, "supports_exit_in_kernel", False) and (
-                    self.exit_in_kernel is True or (self.exit_in_kernel == "auto" and -(-B // 16) <= 512)):
-                # launch-bound batch: the whole nonlinear solve with the reference's exit rule in ONE cooperative launch
-                if need_grad and "nlws" not in ws:
-                    ws["nlws"] = be.new_workspace_nonlin(dims, st.z)
-                counts = torch.zeros(self.al_iter, dtype=torch.int32, device=dev)
-                if be.solve_nonlin(dims, st.dx.fused_id, st.dx.dt, Qd, q, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho,
-                                   ws["phi"], rnorm2=ws["rn2"], info=ws["info"], status=ws["status"],
-                                   al_iter=self.al_iter, max_newton=MAX_NEWTON,
-                                   flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE, rho_scale=RHO_SCALE,
-                                   workspace=ws.get("nlws"), newton_counts=counts):
-                    npa = list(counts.unbind())
-                    rho_last = st.rho / RHO_SCALE
-                    if need_grad:
-                        F_last = be.nonlin_F_view(ws["nlws"], dims)
-                    num_iters = 0
-            for _ in range(num_iters):
-                rho_last = st.rho.clone()
-                if fused_nl:
-                    # compiled-in model, reference exit: one launch per Newton step (the model inlined),
-                    # the batch-global exit test on the device, then the dual update launch
-                    if need_grad and "nlws" not in ws:
-                        ws["nlws"] = be.new_workspace_nonlin(dims, st.z)
-                    npa.append(self._newton_al_fused_nl(st, Qd, q, bnd, ws))
-                    be.solve_nonlin(dims, st.dx.fused_id, st.dx.dt, Qd, q, st.x0, lo, hi, sb, stt, st.z, st.lam,
-                                    st.rho, ws["phi"], rnorm2=ws["rn2"], info=None, status=ws["status"],
-                                    al_iter=1, max_newton=0, flags=_abi.ALQP_DUAL_UPDATE, rho_scale=RHO_SCALE,
-                                    workspace=ws.get("nlws"))
-                    if need_grad:   # L and F of the last executed Newton step are still in the workspace
-                        F_last = be.nonlin_F_view(ws["nlws"], dims)
-                    continue
-                if coop and ws.get("coop_ok", True):
-                    # one AL iteration (starting merit, Newton loop with the batch-global exit, dual update) per launch
-                    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-                    save = need_grad and not use_qws
-                    extra = dict(workspace=ws["qws"], variant="quad") if use_qws else {}
-                    wsx = extra.get("workspace")
-                    if wsx is None and hasattr(be, "_workspace"):
-                        wsx = be._workspace(dims, st.z)[0]
-                    pf = _abi.ALQP_WS_PRIMED if (not save and wsx is not None and ws.get("primed") is wsx) else 0
-                    ok = be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho, ws["phi"],
-                                      rnorm2=ws["rn2"], info=ws["info"], status=ws["status"], factor=ws.get("factor"),
-                                      al_iter=1, max_newton=MAX_NEWTON, n_ls=N_LS, rho_scale=RHO_SCALE, newton_counts=cnt,
-                                      flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE | (_abi.ALQP_SAVE_FACTOR if save else 0) | pf,
-                                      **extra)
-                    ws["coop_ok"] = ok
-                    if ok:
-                        ws["primed"] = wsx if getattr(be, "last_variant", None) == "quad" else None
-                        npa.append(cnt[0])
-                        F_last = F
-                        if stream and self._global_max(st.rho) > self.rho_max:
-                            break
-                        continue
-                if F is not None:
-                    npa.append(self._newton_al_lin(st, Qd, q, F, c, bnd, ws, need_grad))
-                    F_last = F
-                else:
-                    npa.append(self._newton_al_nonlin(st, Qd, q, bnd, ws, need_grad))
-                    F_last = ws.get("F_last")
-                # dual update with the TRUE dynamics (AL_mpc.py:315-317 / :397-399)
-                if F is not None and not linearize_once:
-                    # (never on the private workspace: its y/r/s slots may be rewritten, its L not,
-                    #  but keep the saved factor's workspace out of later launches altogether)
-                    wsc = be._workspace(dims, st.z)[0] if hasattr(be, "_workspace") else None
-                    pf = _abi.ALQP_WS_PRIMED if (wsc is not None and ws.get("primed") is wsc) else 0
-                    be.solve_lin(dims, Qd, q, F, c, st.x0, lo, hi, sb, stt, st.z, st.lam, st.rho,
-                                 ws["phi"], rnorm2=ws["rn2"], info=None, status=ws["status"],
-                                 al_iter=1, max_newton=0, n_ls=N_LS, flags=_abi.ALQP_DUAL_UPDATE | pf,
-                                 rho_scale=RHO_SCALE)
-                    ws["primed"] = wsc if getattr(be, "last_variant", None) == "quad" else None
-                else:
-                    xn = true_next(st.z)
-                    okw = self._obs_kwargs(dt, dev)
-                    be.merit(dims, 1, st.z, xn, st.x0, st.lam, st.rho, Qd, q, lo, hi, sb, stt,
-                             ws["phi"], ws["rn2"], **okw)
-                    be.dual_update(dims, st.z, xn, st.x0, lo, hi, sb, stt, st.lam, st.rho, RHO_SCALE, **okw)
-                    ws["primed"] = None   # lam/rho changed behind the workspace records' back
-                if stream:
-                    if linearize_once:
-                        mean = self._global_mean(ws["rn2"].sqrt())
-                        if prev_mean is not None and not mean < prev_mean:
-                            break
-                        prev_mean = mean
-                    if self._global_max(st.rho) > self.rho_max:
-                        break
-            if stream and self._global_max(st.rho) > self.rho_max:
-                st.status_flag = True
         # device-side exit counters (one read-back for the whole solve)
-        if any(torch.is_tensor(v) for v in npa):
-            vals = torch.stack([(v[1] if v.numel() == 3 else v.to(torch.float64).reshape(())) if torch.is_tensor(v)
-                                else torch.tensor(float(v), dtype=torch.float64, device=st.z.device)
-                                for v in npa]).tolist()
-            npa = [int(round(v)) for v in vals]
+        on_dev = [i for i, v in enumerate(npa) if torch.is_tensor(v)]
+        if on_dev:
+            for i, v in zip(on_dev, torch.stack([npa[i].to(torch.float64) for i in on_dev]).tolist()):
+                npa[i] = int(round(v))
             if min(npa) < 0:
                 raise RuntimeError("mi_alqp: a grid barrier of the in-kernel exit test timed out (ALQP_EXIT_IN_KERNEL); "
                                    "construct the MPC with exit_in_kernel=False")
         st.newton_per_al = npa
         # (kept raw: `last_status` / `dyn_res_prev` are formed when read - two device kernels per call that a
         #  solve whose caller never looks at them does not pay for; at the reference's batch size a call is ~0.6 ms)
-        self._status_raw = ws["status"]
-        self.last_info = ws["info"]
-        self._rn2_raw = ws["rn2"]
+        self._status_raw = L.status
+        self.last_info = L.info
+        self._rn2_raw = L.rn2
         if self.check_numerics is not None:
-            n_piv = int((ws["info"] != 0).sum().item())
-            n_bad = int((ws["status"] == 0).sum().item())
+            n_piv = int((L.info != 0).sum().item())
+            n_bad = int((L.status == 0).sum().item())
             if n_piv or n_bad:
                 msg = (f"mi_alqp: {n_piv} of {B} instances met a non-positive pivot (penalty x conditioning beyond "
                        f"{dt}; modified-Cholesky step taken, see MPC.last_info), {n_bad} hold a non-finite iterate "
@@ -819,9 +792,9 @@ class MPC(Module):
                 import warnings
                 warnings.warn(msg, RuntimeWarning, stacklevel=3)
         if need_grad and F_last is not None:
-            if "nlws" in ws:
-                return "workspace", ws["nlws"], F_last, rho_last
+            if L.nlws is not None:
+                return "workspace", L.nlws, F_last, rho_last
             if use_qws:
-                return "workspace", ws["qws"], F_last, rho_last
-            return "packed", ws["factor"], F_last, rho_last
+                return "workspace", L.qws, F_last, rho_last
+            return "packed", L.factor, F_last, rho_last
         return None
