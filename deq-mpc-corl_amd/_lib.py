@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_ALQP_LIB") or os.path.join(_HERE, "csrc", "libmi_alqp.so")   # MI_ALQP_LIB: A/B experiments with a second build of the same ABI
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class AlqpDims(C.Structure):
@@ -86,6 +86,9 @@ _SIGS = {
                                    C.c_double, _P]),
     "alqp_backward": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P]),
     "alqp_backward_ws": (C.c_int, [C.POINTER(AlqpDims), _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "alqp_backward_dyn": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, _P, _P, _P, _P]),
+    "alqp_backward_ws_dyn": (C.c_int, [C.POINTER(AlqpDims), _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, C.c_long,
+                                       _P, _P, _P, _P]),
     "alqp_newton_step_obs": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                        C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, _P, _P, _P, _P]),
     "alqp_merit_obs": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,

@@ -47,6 +47,39 @@ def _stream():
 _DEBUG_FLAGS = ((int(os.environ.get("ALQP_DEBUG_STAGGER", "0")) & 0xff) << 24) | ((int(os.environ.get("ALQP_DEBUG_STAGGER_CU", "0")) & 0xf) << 20)
 
 
+class DynGrads:
+    """What `backward` / `backward_ws` take as `dyn=`: the outputs for the gradients w.r.t. the affine dynamics
+    x_{t+1} = F_t z_t + c_t and the initial state (include/mi_alqp.h, alqp_backward_dyn_*). `lam` [B, >= (T-1) nx]
+    holds the multipliers the solve returned (rows may be a view of the full lam: only a unit inner stride is
+    needed; required with dF). dF [B, T-1, nx, n], dc [B, T-1, nx], dx0 [B, nx]: a tensor to fill, or None."""
+
+    __slots__ = ("lam", "dF", "dc", "dx0")
+
+    def __init__(self, lam=None, dF=None, dc=None, dx0=None):
+        self.lam, self.dF, self.dc, self.dx0 = lam, dF, dc, dx0
+
+
+def _dyn_args(dyn, dims, dt):
+    B, T, nx, nu = dims
+    lam = dyn.lam
+    if lam is None:
+        if dyn.dF is not None:
+            raise ValueError("mi_alqp: dyn.dF needs dyn.lam (the multipliers the solve returned)")
+        lam_p, sb = None, 0
+    else:
+        if (not lam.is_cuda or lam.dtype != dt or lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < (T - 1) * nx
+                or lam.stride(1) != 1 or (B > 1 and lam.stride(0) < (T - 1) * nx)):
+            raise ValueError(f"mi_alqp: dyn.lam must be a [B, >= (T-1) nx] {dt} device tensor with unit inner stride")
+        lam_p, sb = C.c_void_p(lam.data_ptr()), max(int(lam.stride(0)), (T - 1) * nx)
+    outs = []
+    for t, name, shape in ((dyn.dF, "dF", (B, T - 1, nx, nx + nu)), (dyn.dc, "dc", (B, T - 1, nx)),
+                           (dyn.dx0, "dx0", (B, nx))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"mi_alqp: dyn.{name} has shape {tuple(t.shape)}, expected {shape}")
+        outs.append(_ptr(t, "dyn." + name, dt, allow_none=True))
+    return [lam_p, sb] + outs
+
+
 class HipBackend:
     """The product backend: thin argument marshalling over the C ABI."""
 
@@ -400,16 +433,19 @@ class HipBackend:
             rc = getattr(self.lib, "alqp_dual_update_obs_" + sfx)(*head, C.byref(o), *tail)
         _lib.check(rc, "alqp_dual_update_" + sfx)
 
-    def backward(self, dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad):
+    def backward(self, dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad, dyn=None):
+        """w = -H^{-1} gbar with the packed factor -> q_grad, Qd_grad; with dyn (a DynGrads) also dF / dc / dx0."""
         B, T, nx, nu = dims
         dt = gbar.dtype
         sfx = _dt(gbar)
         d = _lib.AlqpDims(B, T, nx, nu)
-        fn = getattr(self.lib, "alqp_backward_" + sfx)
+        name = ("alqp_backward_" if dyn is None else "alqp_backward_dyn_") + sfx
+        fn = getattr(self.lib, name)
+        extra = [] if dyn is None else _dyn_args(dyn, dims, dt)
         rc = fn(C.byref(d), _ptr(factor, "factor", dt), _ptr(F, "F", dt), _ptr(rho, "rho", dt),
                 _ptr(z_final, "z_final", dt), _ptr(gbar, "gbar", dt), _ptr(q_grad, "q_grad", dt),
-                _ptr(Qd_grad, "Qd_grad", dt), _stream())
-        _lib.check(rc, "alqp_backward_" + sfx)
+                _ptr(Qd_grad, "Qd_grad", dt), *extra, _stream())
+        _lib.check(rc, name)
 
 
     def new_workspace_nonlin(self, dims, like):
@@ -431,16 +467,18 @@ class HipBackend:
         need = self.workspace_bytes(*dims, like.dtype)
         return torch.empty(need // like.element_size() + 16, dtype=like.dtype, device=like.device)
 
-    def backward_ws(self, dims, workspace, F, rho, z_final, gbar, q_grad, Qd_grad):
+    def backward_ws(self, dims, workspace, F, rho, z_final, gbar, q_grad, Qd_grad, dyn=None):
         B, T, nx, nu = dims
         dt = gbar.dtype
         sfx = _dt(gbar)
         d = _lib.AlqpDims(B, T, nx, nu)
-        fn = getattr(self.lib, "alqp_backward_ws_" + sfx)
+        name = ("alqp_backward_ws_" if dyn is None else "alqp_backward_ws_dyn_") + sfx
+        fn = getattr(self.lib, name)
+        extra = [] if dyn is None else _dyn_args(dyn, dims, dt)
         rc = fn(C.byref(d), _ptr(workspace, "workspace", dt), self.workspace_bytes(*dims, dt),
                 _ptr(F, "F", dt), _ptr(rho, "rho", dt), _ptr(z_final, "z_final", dt),
-                _ptr(gbar, "gbar", dt), _ptr(q_grad, "q_grad", dt), _ptr(Qd_grad, "Qd_grad", dt), _stream())
-        _lib.check(rc, "alqp_backward_ws_" + sfx)
+                _ptr(gbar, "gbar", dt), _ptr(q_grad, "q_grad", dt), _ptr(Qd_grad, "Qd_grad", dt), *extra, _stream())
+        _lib.check(rc, name)
 
 
     # ---- interior-point path (csrc/alqp_ipm.hip) -------------------------------------------------

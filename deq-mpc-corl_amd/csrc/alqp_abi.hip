@@ -179,33 +179,63 @@ int newton_step_impl(const AlqpDims *dims, const void *z, const void *xnext, con
     return dispatch_step<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
 }
 
-template <typename real>
-int backward_impl(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
-                  const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, void *stream) {
-    if (!dims_ok(dims) || !factor || !F || !rho || !z_final || !gbar || !q_grad || !Qd_grad)
-        return ALQP_E_BADARG;
-    BwdArgs<real> a = {};
+// the dynamics-gradient outputs of alqp_backward_dyn_* / alqp_backward_ws_dyn_* (all null: the plain backward)
+struct BwdDyn {
+    const void *lam = nullptr;
+    long sb_lam = 0;
+    void *dF = nullptr, *dc = nullptr, *dx0 = nullptr;
+};
+template <typename real, bool DYN>
+void set_bwd(const AlqpDims *dims, const void *factor, const void *F, const void *rho, const void *z_final,
+             const void *gbar, void *q_grad, void *Qd_grad, BwdArgs<real, DYN> &a) {
     a.B = dims->B; a.T = dims->T;
     a.factor = (const real *)factor; a.F = (const real *)F; a.rho = (const real *)rho;
     a.z_final = (const real *)z_final; a.gbar = (const real *)gbar;
     a.q_grad = (real *)q_grad; a.Qd_grad = (real *)Qd_grad;
-    return dispatch_backward<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
+}
+template <typename real>
+bool set_dyn(const AlqpDims *dims, const BwdDyn &d, BwdArgs<real, true> &a) {
+    if (d.dF && (!d.lam || d.sb_lam < (long)(dims->T - 1) * dims->nx)) return false;
+    a.lam = (const real *)d.lam; a.sb_lam = d.sb_lam;
+    a.dF = (real *)d.dF; a.dc = (real *)d.dc; a.dx0 = (real *)d.dx0;
+    return true;
+}
+
+template <typename real>
+int backward_impl(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
+                  const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, void *stream,
+                  const BwdDyn *dyn = nullptr) {
+    if (!dims_ok(dims) || !factor || !F || !rho || !z_final || !gbar || !q_grad || !Qd_grad)
+        return ALQP_E_BADARG;
+    if (dyn) {
+        BwdArgs<real, true> a = {};
+        set_bwd(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad, a);
+        if (!set_dyn(dims, *dyn, a)) return ALQP_E_BADARG;
+        return dispatch_backward<real, true>(dims->nx, dims->nu, a, (hipStream_t)stream);
+    }
+    BwdArgs<real> a = {};
+    set_bwd(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad, a);
+    return dispatch_backward<real, false>(dims->nx, dims->nu, a, (hipStream_t)stream);
 }
 
 template <typename real>
 int backward_ws_impl(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F, const void *rho,
-                     const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, void *stream) {
+                     const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, void *stream,
+                     const BwdDyn *dyn = nullptr) {
     if (!dims_ok(dims) || !workspace || !F || !rho || !z_final || !gbar || !q_grad || !Qd_grad)
         return ALQP_E_BADARG;
     const size_t need = quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
     if (need == 0) return ALQP_E_UNSUPPORTED;
     if (ws_bytes < need) return ALQP_E_BADARG;
+    if (dyn) {
+        BwdArgs<real, true> a = {};
+        set_bwd(dims, nullptr, F, rho, z_final, gbar, q_grad, Qd_grad, a);
+        if (!set_dyn(dims, *dyn, a)) return ALQP_E_BADARG;
+        return dispatch_backward_quad<real, true>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
+    }
     BwdArgs<real> a = {};
-    a.B = dims->B; a.T = dims->T;
-    a.F = (const real *)F; a.rho = (const real *)rho;
-    a.z_final = (const real *)z_final; a.gbar = (const real *)gbar;
-    a.q_grad = (real *)q_grad; a.Qd_grad = (real *)Qd_grad;
-    return dispatch_backward_quad<real>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
+    set_bwd(dims, nullptr, F, rho, z_final, gbar, q_grad, Qd_grad, a);
+    return dispatch_backward_quad<real, false>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
 }
 
 }  // namespace alqp
@@ -213,7 +243,7 @@ int backward_ws_impl(const AlqpDims *dims, void *workspace, size_t ws_bytes, con
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 10; }
+int alqp_abi_version(void) { return 11; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -340,5 +370,25 @@ int alqp_backward_ws_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes,
                          void *Qd_grad, void *stream) {
     return alqp::backward_ws_impl<double>(dims, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, stream);
 }
+
+#define ALQP_DEFINE_BWD_DYN(SFX, REAL)                                                                \
+    int alqp_backward_dyn_##SFX(const AlqpDims *dims, const void *factor, const void *F, const void *rho, \
+                                const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,   \
+                                const void *lam, long sb_lam, void *dF, void *dc, void *dx0,          \
+                                void *stream) {                                                       \
+        const alqp::BwdDyn d = {lam, sb_lam, dF, dc, dx0};                                            \
+        return alqp::backward_impl<REAL>(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad,        \
+                                         stream, &d);                                                 \
+    }                                                                                                 \
+    int alqp_backward_ws_dyn_##SFX(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F, \
+                                   const void *rho, const void *z_final, const void *gbar,            \
+                                   void *q_grad, void *Qd_grad, const void *lam, long sb_lam,         \
+                                   void *dF, void *dc, void *dx0, void *stream) {                     \
+        const alqp::BwdDyn d = {lam, sb_lam, dF, dc, dx0};                                            \
+        return alqp::backward_ws_impl<REAL>(dims, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, \
+                                            Qd_grad, stream, &d);                                     \
+    }
+ALQP_DEFINE_BWD_DYN(f32, float)
+ALQP_DEFINE_BWD_DYN(f64, double)
 
 }  // extern "C"

@@ -107,11 +107,20 @@ struct StepArgs {
     int no_init;       // state-estimator row set (AlqpObstacles.state_estimator)
 };
 
-template <typename real>
+// DYN = false: the plain backward (alqp_backward_*), the kernel arguments it always had. DYN = true (alqp_backward_dyn_*)
+// adds the gradients w.r.t. the affine dynamics and the initial state behind them, in a type of its own so that the
+// plain kernels' argument block, and with it their code, stays what it was.
+template <typename real, bool DYN = false>
 struct BwdArgs {
     int B, T;
     const real *factor, *F, *rho, *z_final, *gbar;
     real *q_grad, *Qd_grad;
+};
+template <typename real>
+struct BwdArgs<real, true> : BwdArgs<real, false> {
+    const real *lam;       // the multipliers the solve returned; rows [0, (T-1) nx) of an instance are read
+    long sb_lam;           // words from one instance's lam to the next
+    real *dF, *dc, *dx0;   // nullable each: [B][T-1][nx][n], [B][T-1][nx], [B][nx]
 };
 
 // A VGPR zero the compiler cannot see through: keeps LDS addresses "divergent", so that

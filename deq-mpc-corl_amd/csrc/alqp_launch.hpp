@@ -46,8 +46,8 @@ template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream);
-template <typename real>
-int dispatch_backward(int nx, int nu, const BwdArgs<real> &a, hipStream_t stream);
+template <typename real, bool DYN>
+int dispatch_backward(int nx, int nu, const BwdArgs<real, DYN> &a, hipStream_t stream);
 template <typename real>
 size_t lds_query(int nx, int nu, int T);   // bytes of the team LDS image, 0: no such instance
 
@@ -55,8 +55,8 @@ size_t lds_query(int nx, int nu, int T);   // bytes of the team LDS image, 0: no
 template <typename real>
 int dispatch_solve_quad(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, real *ws,
                         hipStream_t stream);
-template <typename real>
-int dispatch_backward_quad(int nx, int nu, const BwdArgs<real> &a, real *ws, hipStream_t stream);
+template <typename real, bool DYN>
+int dispatch_backward_quad(int nx, int nu, const BwdArgs<real, DYN> &a, real *ws, hipStream_t stream);
 template <typename real>
 int dispatch_solve_nonlin(int dyn_id, int nx, int nu, const SolveArgs<real> &a, real *ws, hipStream_t stream);
 template <typename real>

@@ -1,5 +1,8 @@
 // alqp_quad.hip - the quad kernels (4 lanes per QP, registers + DPP, HBM workspace: alqp_quad.hpp) and their
 // launchers. Compiled once per dtype (-DALQP_QUAD_F32 / -DALQP_QUAD_F64), one object each.
+#ifdef ALQP_BWD_DYN_UNIT
+#undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
+#endif
 #include <hip/hip_runtime.h>
 
 #include "alqp_quad.hpp"
@@ -224,8 +227,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 // ---- backward of the implicit layer, quad variant: the factor is the workspace a previous
 //      quad solve left behind (per-stage lower triangles of L) ---------------------------------
-template <typename real, int NX, int NU>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_backward_quad(BwdArgs<real> a, real *ws) {
+// DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_ws_dyn_*). w_t is
+// the record's y/d field; a lane owns rows i = q (mod 4) of F_t as in the sweeps and, per own row, forms
+// s_t[i] = w_{t+1}[i] - F_t[i] . w_t from F and w (the record's s group is not relied on) and writes the row of dF_t.
+template <typename real, int NX, int NU, bool DYN = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_backward_quad(BwdArgs<real, DYN> a, real *ws) {
     using C = QCfg<real, NX, NU>;
     constexpr int N = C::N;
     const int lane = threadIdx.x, qi = lane >> 2;
@@ -259,6 +265,49 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 qg[t * N + j] = w;
                 Qg[t * N + j] = w * zf[t * N + j];
             }
+    }
+    if constexpr (DYN) {
+        constexpr int SW = C::SW;
+        const real rho = qd.rho;
+        const size_t bd = (size_t)b * (T - 1) * NX;   // this instance's first dynamics row
+        const real *zf = a.z_final + (size_t)b * T * N;
+        const real *lm = a.lam ? a.lam + (size_t)b * a.sb_lam : nullptr;
+        for (int t = 0; t + 1 < T; ++t) {
+            real wt[N], wnx[SW];
+            qd.ld_rep_n(qd.recp(t) + C::oY, wt);
+            qd.ld_ownx_of_n(qd.recp(t + 1) + C::oY, wnx);
+            real zt[N];
+            if (a.dF) gload<N>(zf + t * N, zt);
+#pragma unroll
+            for (int s = 0; s < SW; ++s) {
+                const int r = 4 * s + qd.q;
+                const bool own = (4 * s + 3 < NX || r < NX) && active;   // padding quads alias instance B - 1: no writes
+                const int rc = (4 * s + 3 < NX || r < NX) ? r : NX - 1;
+                real fr[N];
+                gload<N>(qd.gF + ((size_t)t * NX + rc) * N, fr);
+                real p = 0;
+#pragma unroll
+                for (int k = 0; k < N; ++k) p = fma_(fr[k], wt[k], p);
+                const real si = wnx[s] - p;
+                if (a.dF) {
+                    const real v = lm[t * NX + rc];
+                    real row[N];
+#pragma unroll
+                    for (int k = 0; k < N; ++k) row[k] = -v * wt[k] - rho * si * zt[k];
+                    if (own) qd.template gstore<N>(a.dF + (bd + (size_t)t * NX + r) * N, row);
+                }
+                if (a.dc && own) a.dc[bd + (size_t)t * NX + r] = -rho * si;
+            }
+        }
+        if (a.dx0) {
+            real w0[SW];
+            qd.ld_ownx_of_n(qd.recp(0) + C::oY, w0);
+#pragma unroll
+            for (int s = 0; s < SW; ++s) {
+                const int r = 4 * s + qd.q;
+                if ((4 * s + 3 < NX || r < NX) && active) a.dx0[(size_t)b * NX + r] = -rho * w0[s];
+            }
+        }
     }
 }
 
@@ -327,10 +376,10 @@ int dispatch_solve_quad(int nx, int nu, const SolveArgs<real> &a, const TraceArg
     });
 }
 
-template <typename real>
-int dispatch_backward_quad(int nx, int nu, const BwdArgs<real> &a, real *ws, hipStream_t stream) {
+template <typename real, bool DYN>
+int dispatch_backward_quad(int nx, int nu, const BwdArgs<real, DYN> &a, real *ws, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
-        return launch_quad_kernel<real, NX, NU>(k_backward_quad<real, NX, NU>, a.B, stream, a, ws);
+        return launch_quad_kernel<real, NX, NU>(k_backward_quad<real, NX, NU, DYN>, a.B, stream, a, ws);
     });
 }
 
@@ -364,10 +413,16 @@ using quad_real = float;
 #else
 using quad_real = double;
 #endif
+// The DYN instantiations of k_backward_quad are a compile unit of their own per dtype (-DALQP_BWD_DYN_UNIT, build.sh): the
+// unit every other quad kernel comes out of then holds exactly the instantiations it held before they existed.
+#ifndef ALQP_BWD_DYN_UNIT
 template int dispatch_solve_quad<quad_real>(int, int, const SolveArgs<quad_real> &, const TraceArgs<quad_real> *, quad_real *, hipStream_t);
-template int dispatch_backward_quad<quad_real>(int, int, const BwdArgs<quad_real> &, quad_real *, hipStream_t);
+template int dispatch_backward_quad<quad_real, false>(int, int, const BwdArgs<quad_real, false> &, quad_real *, hipStream_t);
 template int dispatch_solve_nonlin<quad_real>(int, int, int, const SolveArgs<quad_real> &, quad_real *, hipStream_t);
 template int dispatch_step_quad<quad_real>(int, int, const StepArgs<quad_real> &, quad_real *, hipStream_t);
+#else
+template int dispatch_backward_quad<quad_real, true>(int, int, const BwdArgs<quad_real, true> &, quad_real *, hipStream_t);
+#endif
 
 }  // namespace alqp
 

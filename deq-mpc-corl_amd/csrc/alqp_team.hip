@@ -1,5 +1,8 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
+#ifdef ALQP_BWD_DYN_UNIT
+#undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
+#endif
 #include <hip/hip_runtime.h>
 
 #include "alqp_team.hpp"
@@ -241,8 +244,12 @@ __global__ __launch_bounds__(64) void k_newton_step(StepArgs<real> a) {
 }
 
 // ---- backward of the implicit layer -------------------------------------------------
-template <typename real, int NX, int NU>
-__global__ __launch_bounds__(64) void k_backward(BwdArgs<real> a) {
+// DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_dyn_*). With
+// w = -H^{-1} gbar in ds, s_t = w_{t+1}[x] - F_t w_t in seq (what backward_sweep leaves there as (J d)_eq) and
+// v_t = the returned lam's dynamics rows: dF_t[i][j] = -v_t[i] w_t[j] - rho s_t[i] z_t[j], dc_t[i] = -rho s_t[i],
+// dx0[i] = -rho w_0[i].
+template <typename real, int NX, int NU, bool DYN = false>
+__global__ __launch_bounds__(64) void k_backward(BwdArgs<real, DYN> a) {
     using C = Cfg<real, NX, NU>;
     constexpr int G = C::G, N = C::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -272,6 +279,32 @@ __global__ __launch_bounds__(64) void k_backward(BwdArgs<real> a) {
             real w = tm.ds[e];
             qg[e] = w;
             Qg[e] = w * zf[e];
+        }
+    }
+    if constexpr (DYN) {
+        // z_final and v into the slabs the backward pass leaves unused (zs, req); every team has its own
+        const real *zf = a.z_final + (size_t)b * T * N;
+        const int ND = (T - 1) * NX;
+        if (a.dF) {
+            const real *lm = a.lam + (size_t)b * a.sb_lam;
+            for (int e = li; e < T * N; e += G) tm.zs[e] = zf[e];
+            for (int e = li; e < ND; e += G) tm.req[e] = lm[e];
+        }
+        wave_sync();
+        if (active) {
+            const real rho = tm.rho;
+            if (a.dF) {
+                real *gd = a.dF + (size_t)b * ND * N;
+                for (int e = li; e < ND * N; e += G) {
+                    const int ti = e / N, j = e - ti * N, t = ti / NX;   // ti = t * NX + i
+                    gd[e] = -tm.req[ti] * tm.ds[t * N + j] - rho * tm.seq[ti] * tm.zs[t * N + j];
+                }
+            }
+            if (a.dc) {
+                real *gd = a.dc + (size_t)b * ND;
+                for (int e = li; e < ND; e += G) gd[e] = -rho * tm.seq[e];
+            }
+            if (a.dx0 && li < NX) a.dx0[(size_t)b * NX + li] = -rho * tm.ds[li];
         }
     }
 }
@@ -329,10 +362,10 @@ int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream) {
     });
 }
 
-template <typename real>
-int dispatch_backward(int nx, int nu, const BwdArgs<real> &a, hipStream_t stream) {
+template <typename real, bool DYN>
+int dispatch_backward(int nx, int nu, const BwdArgs<real, DYN> &a, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
-        return launch_team_kernel<real, NX, NU>(k_backward<real, NX, NU>, a.B, a.T, stream, a);
+        return launch_team_kernel<real, NX, NU>(k_backward<real, NX, NU, DYN>, a.B, a.T, stream, a);
     });
 }
 
@@ -341,14 +374,21 @@ size_t lds_query(int nx, int nu, int T) {
     return for_dims(nx, nu, size_t(0), [&](auto NX, auto NU) { return lds_bytes_for<real, NX, NU>(T); });
 }
 
+// The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
+// other team kernel comes out of then holds exactly the instantiations it held before they existed.
+#ifndef ALQP_BWD_DYN_UNIT
 template int dispatch_solve<float>(int, int, const SolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve<double>(int, int, const SolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 template int dispatch_step<float>(int, int, const StepArgs<float> &, hipStream_t);
 template int dispatch_step<double>(int, int, const StepArgs<double> &, hipStream_t);
-template int dispatch_backward<float>(int, int, const BwdArgs<float> &, hipStream_t);
-template int dispatch_backward<double>(int, int, const BwdArgs<double> &, hipStream_t);
+template int dispatch_backward<float, false>(int, int, const BwdArgs<float, false> &, hipStream_t);
+template int dispatch_backward<double, false>(int, int, const BwdArgs<double, false> &, hipStream_t);
 template size_t lds_query<float>(int, int, int);
 template size_t lds_query<double>(int, int, int);
+#else
+template int dispatch_backward<float, true>(int, int, const BwdArgs<float, true> &, hipStream_t);
+template int dispatch_backward<double, true>(int, int, const BwdArgs<double, true> &, hipStream_t);
+#endif
 
 }  // namespace alqp
 

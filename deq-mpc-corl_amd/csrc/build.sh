@@ -21,6 +21,9 @@ alqp_team        alqp_team.hip
 alqp_aux         alqp_aux.hip
 alqp_quad_f32    alqp_quad.hip        -DALQP_QUAD_F32
 alqp_quad_f64    alqp_quad.hip        -DALQP_QUAD_F64
+alqp_team_dyn      alqp_team.hip      -DALQP_BWD_DYN_UNIT
+alqp_quad_dyn_f32  alqp_quad.hip      -DALQP_QUAD_F32 -DALQP_BWD_DYN_UNIT
+alqp_quad_dyn_f64  alqp_quad.hip      -DALQP_QUAD_F64 -DALQP_BWD_DYN_UNIT
 alqp_dyn_casadi  alqp_dyn_casadi.hip
 alqp_ipm         alqp_ipm.hip
 alqp_ipm_g4_f64  alqp_ipm_g4.hip      -DALQP_G4_F64

@@ -146,39 +146,64 @@ class _ALSolve(torch.autograd.Function):
     """The whole AL solve as one differentiable node.
 
     Like the reference, only the LAST AL iteration is differentiated (earlier ones
-    are cut by ``.detach().clone()``, AL_mpc.py:299) and only w.r.t. q and diag(Q)
+    are cut by ``.detach().clone()``, AL_mpc.py:299) and w.r.t. q and diag(Q)
     (NewtonAL.backward, al_utils.py:578-615): w = -H^{-1} gbar with the factor saved
     at the last executed Newton step, q_grad = w, Q_grad = w * z_final.
+
+    Beyond the reference, on the affine (``LinDx``) routes: when ``LinDx.F``, ``LinDx.f`` or ``x0`` requires grad they
+    are the inputs ``dyn = (F, f, x0)`` and get dF, dc, dx0 of include/mi_alqp.h (alqp_backward_dyn_*) out of the same
+    w, with the same approximations (multipliers and active set held fixed, factor of the last executed Newton step);
+    the multipliers in those formulas are the equality rows of the lam the solve returned, cloned here. With a callable
+    ``dx`` nothing of this applies: ``x0.grad`` stays None there.
     """
 
     @staticmethod
-    def forward(ctx, Qd, q, st):
+    def forward(ctx, Qd, q, st, *dyn):
         mpc = st.mpc
-        need_grad = Qd.requires_grad or q.requires_grad
+        need_grad = Qd.requires_grad or q.requires_grad or any(t.requires_grad for t in dyn)
         with torch.no_grad():
             saved = mpc._run(st, Qd.detach().contiguous(), q.detach().contiguous(), need_grad)
         ctx.mpc = mpc
         ctx.has_factor = saved is not None
+        ctx.n_dyn = len(dyn)
+        ctx.dyn_dtypes = tuple(t.dtype for t in dyn)
         if saved is not None:
             kind, factor, F_last, rho_last = saved
             ctx.factor_kind = kind  # "packed" (team kernels) or "workspace" (quad solve's workspace)
-            ctx.save_for_backward(factor, F_last, rho_last, st.z)
+            lam_eq = ()
+            if dyn and dyn[0].requires_grad:   # only dF reads the multipliers
+                lam_eq = (st.lam[:, :(mpc.T - 1) * mpc.n_state].clone(),)
+            ctx.save_for_backward(factor, F_last, rho_last, st.z, *lam_eq)
         ctx.dims = (st.z.shape[0], mpc.T, mpc.n_state, mpc.n_ctrl)
         return st.z.clone()
 
     @staticmethod
     def backward(ctx, gz):
         if not ctx.has_factor:
-            return None, None, None
-        factor, F_last, rho_last, z_final = ctx.saved_tensors
+            return (None,) * (3 + ctx.n_dyn)
+        factor, F_last, rho_last, z_final, *lam_eq = ctx.saved_tensors
         gbar = gz.to(z_final.dtype).contiguous()
         q_grad = torch.empty_like(z_final)
         Qd_grad = torch.empty_like(z_final)
+        kw, outs = {}, ()
+        want = ctx.needs_input_grad[3:]
+        if any(want):
+            from deq_mpc_corl_amd.backend import DynGrads
+            B, T, nx, nu = ctx.dims
+            new = lambda *shape: torch.empty(*shape, dtype=z_final.dtype, device=z_final.device)
+            outs = (new(B, T - 1, nx, nx + nu) if want[0] else None, new(B, T - 1, nx) if want[1] else None,
+                    new(B, nx) if want[2] else None)
+            kw["dyn"] = DynGrads(lam_eq[0] if want[0] else None, *outs)   # passed only when asked for
         if ctx.factor_kind == "workspace":
-            ctx.mpc.backend.backward_ws(ctx.dims, factor, F_last, rho_last, z_final, gbar, q_grad, Qd_grad)
+            ctx.mpc.backend.backward_ws(ctx.dims, factor, F_last, rho_last, z_final, gbar, q_grad, Qd_grad, **kw)
         else:
-            ctx.mpc.backend.backward(ctx.dims, factor, F_last, rho_last, z_final, gbar, q_grad, Qd_grad)
-        return Qd_grad, q_grad, None
+            ctx.mpc.backend.backward(ctx.dims, factor, F_last, rho_last, z_final, gbar, q_grad, Qd_grad, **kw)
+        if not ctx.n_dyn:
+            return Qd_grad, q_grad, None
+        if not outs:
+            outs = (None,) * 3
+        return (Qd_grad, q_grad, None,
+                *(None if g is None else g.to(d) for g, d in zip(outs, ctx.dyn_dtypes)))
 
 
 class MPC(Module):
@@ -187,6 +212,11 @@ class MPC(Module):
 
         min_{x,u} sum_t 1/2 tau_t' C_t tau_t + c_t' tau_t     tau_t = [x_t; u_t]
         s.t.      x_{t+1} = f(x_t, u_t),  x_0 = x_init,  u_lower <= u <= u_upper
+
+    Differentiable w.r.t. the cost (diag C and c, as the reference). With affine dynamics given as ``LinDx(F, f)`` (F
+    [B,T-1,nx,n], f [B,T-1,nx], no broadcast over the batch) the solve is also differentiable w.r.t. ``F``, ``f`` and
+    ``x0`` (see ``_ALSolve``); not on the streaming route (``NotImplementedError``). With a callable ``dx`` there are
+    no such gradients: ``x0.grad`` stays ``None``.
     """
 
     def __init__(self, n_state, n_ctrl, T, u_lower=None, u_upper=None, u_init=None, x_init=None,
@@ -499,13 +529,30 @@ class MPC(Module):
         st.lin = self._as_lindx(dx, B)
         st.stream_mode = stream_mode
         st.status_flag = False
-        z = _ALSolve.apply(Qd.to(dt), q.to(dt), st)
+        z = _ALSolve.apply(Qd.to(dt), q.to(dt), st, *self._dyn_inputs(st, x0, stream_mode))
         self.lamda_prev = st.lam[:, :self.neq].contiguous() if self.state_estimator else st.lam
         self.rho_prev = st.rho.reshape(B, 1)
         self.just_initialized = False
         self.last_newton_per_al = st.newton_per_al
         nx = self.n_state
         return z[..., :nx].float(), z[..., nx:].float(), st.status_flag
+
+    def _dyn_inputs(self, st, x0, stream_mode):
+        """(F, f, x0) as inputs of the autograd node when the affine dynamics or the initial state ask for a gradient
+        (_ALSolve), else (): the node, and every launch, is then exactly what it is without this feature."""
+        if st.lin is None or not torch.is_grad_enabled():
+            return ()
+        F, f = st.lin
+        if not (F.requires_grad or (torch.is_tensor(f) and f.requires_grad) or x0.requires_grad):
+            return ()
+        if stream_mode or self.linearize_once:
+            raise NotImplementedError("MPC: gradients w.r.t. LinDx.F / LinDx.f / x0 exist on the al_solve route only; the "
+                                      "streaming route (al_solve_stream, linearize_once) carries lam and rho over "
+                                      "its iterations on the host and saves no multipliers for them")
+        if tuple(f.shape) != tuple(F.shape[:3]):
+            raise NotImplementedError(f"MPC: a gradient w.r.t. LinDx needs f as [B,T-1,nx]={tuple(F.shape[:3])} "
+                                      f"(no broadcast over the batch), got {tuple(f.shape)}")
+        return F, f, x0
 
     def _linearize(self, st, z):
         """dx_jac at every (x_t, u_t), t < T-1 -> (f(z) [B,T-1,nx], F = [A|B] [B,T-1,nx,n]).

@@ -262,6 +262,36 @@ int alqp_backward_ws_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes,
                          const void *rho, const void *z_final, const void *gbar, void *q_grad,
                          void *Qd_grad, void *stream);
 
+/*
+ * The same two backward passes, which also return the gradients w.r.t. the affine dynamics x_{t+1} = F_t z_t + c_t
+ * and the initial state (the reference has no such gradient). With w = -H^{-1} gbar as above, rho[b] the penalty the
+ * factor was built with (that of the last executed Newton step: the rho the solve returned / rho_scale once a dual
+ * update has grown it), v_t the dynamics rows t nx + i of the multipliers the solve RETURNED (after the dual update
+ * that ends an AL iteration they hold lam + rho r(z_final) on the equality rows) and
+ * s_t = w_{t+1}[0:nx] - F_t w_t:
+ *     dF [b][t][i][j] = -v_t[i] w_t[j] - rho s_t[i] z_final_t[j]      [B][T-1][nx][n]
+ *     dc [b][t][i]    = -rho s_t[i]                                   [B][T-1][nx]
+ *     dx0[b][i]       = -rho w_0[i]                                   [B][nx]
+ * i.e. dL/dtheta = w' dg/dtheta for the merit gradient g = Q z + q + J'(lam + rho r_+), with the multipliers and the
+ * active set held fixed as q_grad / Qd_grad do. lam: instance b at lam + b * sb_lam (words), its first (T-1) nx
+ * entries are read; only dF needs it. dF, dc, dx0 are nullable each (a null output is not computed);
+ * ALQP_E_BADARG when dF is given without lam or with sb_lam < (T-1) nx. q_grad / Qd_grad are those of the plain call.
+ */
+int alqp_backward_dyn_f32(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
+                          const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
+                          const void *lam, long sb_lam, void *dF, void *dc, void *dx0, void *stream);
+int alqp_backward_dyn_f64(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
+                          const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
+                          const void *lam, long sb_lam, void *dF, void *dc, void *dx0, void *stream);
+int alqp_backward_ws_dyn_f32(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
+                             const void *rho, const void *z_final, const void *gbar, void *q_grad,
+                             void *Qd_grad, const void *lam, long sb_lam, void *dF, void *dc, void *dx0,
+                             void *stream);
+int alqp_backward_ws_dyn_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
+                             const void *rho, const void *z_final, const void *gbar, void *q_grad,
+                             void *Qd_grad, const void *lam, long sb_lam, void *dF, void *dc, void *dx0,
+                             void *stream);
+
 /* Library/ABI version, bumped when a signature changes. */
 /*
  * The reference leaves its Newton loop on a BATCH-GLOBAL test (al_utils.py:486,551-564):
