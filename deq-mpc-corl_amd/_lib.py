@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_ALQP_LIB") or os.path.join(_HERE, "csrc", "libmi_alqp.so")   # MI_ALQP_LIB: A/B experiments with a second build of the same ABI
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class AlqpDims(C.Structure):
@@ -34,6 +34,10 @@ class AlqpTrace(C.Structure):
 
 class AlqpObstacles(C.Structure):
     _fields_ = [("pos", C.c_void_p), ("radius", C.c_double), ("nobs", C.c_int), ("state_estimator", C.c_int)]
+
+
+class AlqpBwdDyn(C.Structure):
+    _fields_ = [("lam", C.c_void_p), ("sb_lam", C.c_long), ("dF", C.c_void_p), ("dc", C.c_void_p), ("dx0", C.c_void_p)]
 
 
 class AlqpIpmParams(C.Structure):
@@ -78,27 +82,14 @@ _SIGS = {
                                  C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
                                  C.POINTER(AlqpTrace), _P, C.c_size_t, _P]),
     "alqp_newton_step": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                   C.c_long, C.c_long, _P, _P, _P, _P, _P]),
+                                   C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "alqp_merit": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                             C.c_long, C.c_long, _P, _P, _P]),
+                             C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, _P, _P]),
     "alqp_linesearch_pick": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "alqp_dual_update": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long, _P, _P,
-                                   C.c_double, _P]),
-    "alqp_backward": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P]),
-    "alqp_backward_ws": (C.c_int, [C.POINTER(AlqpDims), _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
-    "alqp_backward_dyn": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, _P, _P, _P, _P]),
-    "alqp_backward_ws_dyn": (C.c_int, [C.POINTER(AlqpDims), _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, C.c_long,
-                                       _P, _P, _P, _P]),
-    "alqp_newton_step_obs": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                       C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, _P, _P, _P, _P]),
-    "alqp_merit_obs": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                 C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, _P, _P]),
-    "alqp_dual_update_obs": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long,
-                                       C.POINTER(AlqpObstacles), _P, _P, C.c_double, _P]),
-    "alqp_newton_step_ws": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                      C.c_long, C.c_long, _P, C.c_size_t, _P, _P, _P, _P]),
-    "alqp_newton_step_ws_obs": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                          C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, C.c_size_t, _P, _P, _P, _P]),
+    "alqp_dual_update": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long,
+                                   C.POINTER(AlqpObstacles), _P, _P, C.c_double, _P]),
+    "alqp_backward": (C.c_int, [C.POINTER(AlqpDims), _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P,
+                                C.POINTER(AlqpBwdDyn), _P]),
     "alqp_merit_pick": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, _P, _P, _P, _P, _P, _P]),
     "alqp_ipm_solve": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpIpmParams), _P, _P, _P, _P, _P, _P, _P,
@@ -111,6 +102,7 @@ _PLAIN = {
     "alqp_abi_version": (C.c_int, []),
     "alqp_supported": (C.c_int, [C.POINTER(AlqpDims), C.c_int]),
     "alqp_supported_variant": (C.c_int, [C.POINTER(AlqpDims), C.c_int, C.c_int]),
+    "alqp_pick_variant": (C.c_int, [C.POINTER(AlqpDims), C.c_int, C.c_int, C.c_long]),
     "alqp_lds_bytes": (C.c_size_t, [C.POINTER(AlqpDims), C.c_int]),
     "alqp_qps_per_wave": (C.c_int, [C.POINTER(AlqpDims), C.c_int]),
     "alqp_workspace_bytes": (C.c_size_t, [C.POINTER(AlqpDims), C.c_int]),

@@ -49,7 +49,7 @@ _DEBUG_FLAGS = ((int(os.environ.get("ALQP_DEBUG_STAGGER", "0")) & 0xff) << 24) |
 
 class DynGrads:
     """What `backward` / `backward_ws` take as `dyn=`: the outputs for the gradients w.r.t. the affine dynamics
-    x_{t+1} = F_t z_t + c_t and the initial state (include/mi_alqp.h, alqp_backward_dyn_*). `lam` [B, >= (T-1) nx]
+    x_{t+1} = F_t z_t + c_t and the initial state (include/mi_alqp.h, AlqpBwdDyn). `lam` [B, >= (T-1) nx]
     holds the multipliers the solve returned (rows may be a view of the full lam: only a unit inner stride is
     needed; required with dF). dF [B, T-1, nx, n], dc [B, T-1, nx], dx0 [B, nx]: a tensor to fill, or None."""
 
@@ -60,6 +60,9 @@ class DynGrads:
 
 
 def _dyn_args(dyn, dims, dt):
+    """A DynGrads (or None) -> the AlqpBwdDyn of alqp_backward_* (or None: the plain kernels)."""
+    if dyn is None:
+        return None
     B, T, nx, nu = dims
     lam = dyn.lam
     if lam is None:
@@ -70,14 +73,24 @@ def _dyn_args(dyn, dims, dt):
         if (not lam.is_cuda or lam.dtype != dt or lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < (T - 1) * nx
                 or lam.stride(1) != 1 or (B > 1 and lam.stride(0) < (T - 1) * nx)):
             raise ValueError(f"mi_alqp: dyn.lam must be a [B, >= (T-1) nx] {dt} device tensor with unit inner stride")
-        lam_p, sb = C.c_void_p(lam.data_ptr()), max(int(lam.stride(0)), (T - 1) * nx)
+        lam_p, sb = lam.data_ptr(), max(int(lam.stride(0)), (T - 1) * nx)
     outs = []
     for t, name, shape in ((dyn.dF, "dF", (B, T - 1, nx, nx + nu)), (dyn.dc, "dc", (B, T - 1, nx)),
                            (dyn.dx0, "dx0", (B, nx))):
         if t is not None and tuple(t.shape) != shape:
             raise ValueError(f"mi_alqp: dyn.{name} has shape {tuple(t.shape)}, expected {shape}")
-        outs.append(_ptr(t, "dyn." + name, dt, allow_none=True))
-    return [lam_p, sb] + outs
+        outs.append(None if t is None else _ptr(t, "dyn." + name, dt).value)
+    return _lib.AlqpBwdDyn(lam_p, sb, *outs)
+
+
+def _step_length(h, K, dt):
+    """Step length of the CasADi dynamics providers -> (h, h_pt): a number, or one value per point (a [K] tensor)."""
+    if not torch.is_tensor(h):
+        return float(h), None
+    hpt = h.to(dt).reshape(-1).contiguous()
+    if hpt.numel() != K:
+        raise ValueError("mi_alqp: h must be a number or one value per point")
+    return 0.0, hpt
 
 
 class HipBackend:
@@ -86,15 +99,15 @@ class HipBackend:
     name = "hip"
     supports_exit_in_kernel = True   # solve_lin(newton_counts=...): ALQP_EXIT_IN_KERNEL, cooperative launch
     default_variant = "auto"
-    # "auto": the quad variant (16 instances per wavefront, factor streamed through HBM) wins once
-    # the batch fills the chip; below that the team variant (one instance per lane team, factor in
-    # LDS) has 2-2.4x lower latency (measured on MI355X at (13,4) T=20: B=128 0.83 vs 1.94 ms,
-    # B=4096 2.11 vs 2.08 ms, B=16384 8.2 vs 3.4 ms; (8,2) T=10 crosses near B=5000)
+    # "auto": the quad variant (16 instances per wavefront, factor streamed through HBM) once the batch fills the chip,
+    # the team variant (one instance per lane team, factor in LDS) below. This number is the batch from which the
+    # launch-per-step routes take the quad kernels; the fused solve asks the library (_pick_variant), whose table
+    # (csrc/alqp_abi.hip, with the measurements) this value overrides only when it is changed
     QUAD_MIN_BATCH = 4096
 
     def __init__(self):
         self.lib = _lib.load()
-        self._ws = {}  # (device, dtype) -> scratch tensor for the quad variant (grown on demand)
+        self._ws = {}  # key -> cached scratch tensor (_scratch)
         if os.environ.get("ALQP_QUAD_STAGGER") is not None:   # -1 auto (default), 0 off, > 0 units of ~1024 clocks
             self.set_quad_stagger(int(os.environ["ALQP_QUAD_STAGGER"]))
 
@@ -115,12 +128,15 @@ class HipBackend:
         """Device scratch for the quad variant, cached per (device, dtype). Contents need
         not survive between calls; stream order protects reuse on one stream."""
         need = self.workspace_bytes(*dims, like.dtype)
-        key = (like.device, like.dtype)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() * ws.element_size() < need:
-            ws = torch.empty(need // like.element_size() + 16, dtype=like.dtype, device=like.device)
-            self._ws[key] = ws
-        return ws, need
+        return self._scratch((like.device, like.dtype), need // like.element_size(), like.dtype, like.device, 16), need
+
+    def _scratch(self, key, numel, dtype, device, spare=0):
+        """self._ws[key]: the cached scratch tensor under `key`; allocated anew, with `numel + spare` elements, when it
+        is missing or holds fewer than `numel`."""
+        t = self._ws.get(key)
+        if t is None or t.numel() < numel:
+            t = self._ws[key] = torch.empty(numel + spare, dtype=dtype, device=device)
+        return t
 
     # -- queries ---------------------------------------------------------------
     def supported(self, B, T, nx, nu, dtype):
@@ -134,6 +150,12 @@ class HipBackend:
     def qps_per_wave(self, B, T, nx, nu, dtype):
         d = _lib.AlqpDims(B, T, nx, nu)
         return int(self.lib.alqp_qps_per_wave(C.byref(d), int(dtype == torch.float64)))
+
+    def _pick_variant(self, dims, dtype, flags):
+        """What "auto" resolves to in solve_lin (alqp_pick_variant): 1 team, 2 quad, 0 no instance of (nx, nu). The
+        library's table, unless QUAD_MIN_BATCH was changed: then quad from that batch on."""
+        qmin = -1 if self.QUAD_MIN_BATCH == HipBackend.QUAD_MIN_BATCH else self.QUAD_MIN_BATCH
+        return int(self.lib.alqp_pick_variant(C.byref(_lib.AlqpDims(*dims)), int(dtype == torch.float64), flags, qmin))
 
     # -- kernels -----------------------------------------------------------------
     def solve_lin(self, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,
@@ -154,18 +176,7 @@ class HipBackend:
             variant = self.default_variant
         vnum = {"auto": 0, "team": 1, "quad": 2}[variant]
         if vnum == 0:
-            # the fused solve stays on the team kernels THROUGH B = 4096 (exactly two fp32 / four fp64 full rounds of
-            # teams; round 3: fp32 1.83 against 2.00 ms, fp64 4.35 against 4.71 ms there, quad ahead from B = 5120 on)
-            # (whole-wavefront teams only - 2n + nx + 1 > 32 rows, where it was measured; smaller teams keep round 2's rule)
-            if self.QUAD_MIN_BATCH != 4096:
-                qmin = self.QUAD_MIN_BATCH
-            elif 2 * (nx + nu) + nx + 1 > 32:
-                qmin = 4097
-            else:
-                qmin = 4608 if dt == torch.float64 else 4096
-            vnum = 1 if ((flags & _lib.ALQP_SAVE_FACTOR) or B < qmin) else 2
-            if vnum == 1 and not (flags & _lib.ALQP_SAVE_FACTOR) and not self.lib.alqp_supported_variant(C.byref(d), int(dt == torch.float64), 1):
-                vnum = 2   # horizon too long for the team's LDS image: the quad kernels run it at any batch
+            vnum = self._pick_variant(dims, dt, flags)   # 0 (no such instance) goes through: the library refuses it
         ws, ws_bytes = (None, 0)
         if vnum == 2:
             if workspace is not None:
@@ -200,11 +211,7 @@ class HipBackend:
 
     def _exit_in_kernel(self, p, B, device, newton_counts, exit_tol):
         """AlqpParams fields of ALQP_EXIT_IN_KERNEL: the cached scratch (arrival counter + 2 x B partial sums)."""
-        key = ("exit", device)
-        scr = self._ws.get(key)
-        if scr is None or scr.numel() < 2 * B + 2:
-            scr = torch.zeros(2 * B + 2, dtype=torch.float64, device=device)
-            self._ws[key] = scr
+        scr = self._scratch(("exit", device), 2 * B + 2, torch.float64, device)
         scr.zero_()   # arrival counter, partial sums, time-out flag
         p.flags |= _lib.ALQP_EXIT_IN_KERNEL
         p.exit_tol = float(exit_tol)
@@ -230,11 +237,7 @@ class HipBackend:
             if ws.numel() * ws.element_size() < need:
                 raise ValueError("mi_alqp: workspace too small")
         else:
-            key = ("nl", z.device, dt)
-            ws = self._ws.get(key)
-            if ws is None or ws.numel() * ws.element_size() < need:
-                ws = torch.empty(need // z.element_size() + 16, dtype=dt, device=z.device)
-                self._ws[key] = ws
+            ws = self._scratch(("nl", z.device, dt), need // z.element_size(), dt, z.device, 16)
         skp = _ptr(skip, "skip", torch.float64, True)
         p = _lib.AlqpParams(al_iter, max_newton, 20, flags, rho_scale, 2, skp.value if skp is not None else None)
         if newton_counts is not None:   # the reference's exit test inside one cooperative launch, see solve_lin
@@ -258,11 +261,9 @@ class HipBackend:
         dt = x.dtype
         xn = torch.empty(K, 2, dtype=dt, device=x.device)
         F = torch.empty(K, 2, 3, dtype=dt, device=x.device) if want_jac else None
-        hpt = h.to(dt).reshape(-1).contiguous() if torch.is_tensor(h) else None
-        if hpt is not None and hpt.numel() != K:
-            raise ValueError("mi_alqp: h must be a number or one value per point")
+        h, hpt = _step_length(h, K, dt)
         fn = getattr(self.lib, "alqp_dyn_pendulum1l_" + _dt(x))
-        rc = fn(K, _ptr(x, "x", dt), _ptr(u, "u", dt), 0.0 if hpt is not None else float(h), _ptr(hpt, "h", dt, True),
+        rc = fn(K, _ptr(x, "x", dt), _ptr(u, "u", dt), h, _ptr(hpt, "h", dt, True),
                 _ptr(xn, "xnext", dt), _ptr(F, "F", dt, True), _stream())
         _lib.check(rc, "alqp_dyn_pendulum1l")
         return xn, F
@@ -275,11 +276,9 @@ class HipBackend:
         dt = x.dtype
         xn = torch.empty(K, 4, dtype=dt, device=x.device)
         J = torch.empty(K, 4, 6, dtype=dt, device=x.device) if want_jac else None
-        hpt = h.to(dt).reshape(-1).contiguous() if torch.is_tensor(h) else None
-        if hpt is not None and hpt.numel() != K:
-            raise ValueError("mi_alqp: h must be a number or one value per point")
+        h, hpt = _step_length(h, K, dt)
         fn = getattr(self.lib, ("alqp_dyn_cartpole1l_v2_" if version == 2 else "alqp_dyn_cartpole1l_") + _dt(x))
-        rc = fn(K, _ptr(x, "x", dt), _ptr(tau, "tau", dt), 0.0 if hpt is not None else float(h), _ptr(hpt, "h", dt, True),
+        rc = fn(K, _ptr(x, "x", dt), _ptr(tau, "tau", dt), h, _ptr(hpt, "h", dt, True),
                 _ptr(xn, "xnext", dt), _ptr(J, "J", dt, True), _stream())
         _lib.check(rc, "alqp_dyn_cartpole1l")
         return xn, J
@@ -290,11 +289,9 @@ class HipBackend:
         dt = x.dtype
         xn = torch.empty(K, 6, dtype=dt, device=x.device)
         J = torch.empty(K, 6, 9, dtype=dt, device=x.device) if want_jac else None
-        hpt = h.to(dt).reshape(-1).contiguous() if torch.is_tensor(h) else None
-        if hpt is not None and hpt.numel() != K:
-            raise ValueError("mi_alqp: h must be a number or one value per point")
+        h, hpt = _step_length(h, K, dt)
         fn = getattr(self.lib, "alqp_dyn_cartpole2l_" + _dt(x))
-        rc = fn(K, _ptr(x, "x", dt), _ptr(tau, "tau", dt), 0.0 if hpt is not None else float(h), _ptr(hpt, "h", dt, True),
+        rc = fn(K, _ptr(x, "x", dt), _ptr(tau, "tau", dt), h, _ptr(hpt, "h", dt, True),
                 _ptr(xn, "xnext", dt), _ptr(J, "J", dt, True), _stream())
         _lib.check(rc, "alqp_dyn_cartpole2l")
         return xn, J
@@ -334,59 +331,41 @@ class HipBackend:
 
     def newton_step(self, dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, d_out,
                     g_out=None, factor=None, info=None, obs=None, workspace=None):
-        """workspace: a quad-variant workspace tensor -> alqp_newton_step_ws (16 instances per wavefront,
+        """workspace: a quad-variant workspace tensor -> the quad kernels (16 instances per wavefront,
         the factor stays in the workspace records for backward_ws); None -> the team kernel
-        (one instance per lane team, optional packed `factor`)."""
+        (one instance per lane team, optional packed `factor`). obs: obstacle rows / the state-estimator row set."""
         B, T, nx, nu = dims
         dt = z.dtype
         sfx = _dt(z)
         d = _lib.AlqpDims(B, T, nx, nu)
+        need = 0
         if workspace is not None:
             if factor is not None:
                 raise ValueError("mi_alqp: the quad Newton step leaves its factor in the workspace records (no packed factor)")
             need = self.workspace_bytes(*dims, dt)
             if workspace.numel() * workspace.element_size() < need:
                 raise ValueError("mi_alqp: workspace too small")
-            head = (C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
-                    _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-                    _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u)
-            tail = (_ptr(workspace, "workspace", dt), need, _ptr(d_out, "d_out", dt), _ptr(g_out, "g_out", dt, True),
-                    _ptr(info, "info", torch.int32, True), _stream())
-            if obs is None:
-                rc = getattr(self.lib, "alqp_newton_step_ws_" + sfx)(*head, *tail)
-            else:   # obstacle rows / the state-estimator row set on the quad kernels
-                o = self._obs_struct(obs, dims, dt)
-                rc = getattr(self.lib, "alqp_newton_step_ws_obs_" + sfx)(*head, C.byref(o), *tail)
-            _lib.check(rc, "alqp_newton_step_ws_" + sfx)
-            self.last_step_kernel = "k_newton_step_quad"
-            return
-        self.last_step_kernel = "k_newton_step"
-        head = (C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt),
-                _ptr(x0, "x0", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt),
-                _ptr(q, "q", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u)
-        tail = (_ptr(d_out, "d_out", dt), _ptr(g_out, "g_out", dt, True),
-                _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True), _stream())
-        if obs is None:
-            rc = getattr(self.lib, "alqp_newton_step_" + sfx)(*head, *tail)
-        else:
-            o = self._obs_struct(obs, dims, dt)
-            rc = getattr(self.lib, "alqp_newton_step_obs_" + sfx)(*head, C.byref(o), *tail)
+        o = self._obs_struct(obs, dims, dt) if obs is not None else None
+        rc = getattr(self.lib, "alqp_newton_step_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, C.byref(o) if o is not None else None,
+            _ptr(workspace, "workspace", dt, True), need, _ptr(d_out, "d_out", dt), _ptr(g_out, "g_out", dt, True),
+            _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True), _stream())
         _lib.check(rc, "alqp_newton_step_" + sfx)
+        self.last_step_kernel = "k_newton_step" if workspace is None else "k_newton_step_quad"
 
     def merit(self, dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, phi, rnorm2=None, obs=None):
         B, T, nx, nu = dims
         dt = zc.dtype
         sfx = _dt(zc)
         d = _lib.AlqpDims(B, T, nx, nu)
-        head = (C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
-                _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-                _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u)
-        tail = (_ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True), _stream())
-        if obs is None:
-            rc = getattr(self.lib, "alqp_merit_" + sfx)(*head, *tail)
-        else:
-            o = self._obs_struct(obs, dims, dt)
-            rc = getattr(self.lib, "alqp_merit_obs_" + sfx)(*head, C.byref(o), *tail)
+        o = self._obs_struct(obs, dims, dt) if obs is not None else None
+        rc = getattr(self.lib, "alqp_merit_" + sfx)(
+            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, C.byref(o) if o is not None else None,
+            _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True), _stream())
         _lib.check(rc, "alqp_merit_" + sfx)
 
     def merit_pick(self, dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, z, phi_prev,
@@ -423,30 +402,28 @@ class HipBackend:
         dt = z.dtype
         sfx = _dt(z)
         d = _lib.AlqpDims(B, T, nx, nu)
-        head = (C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
-                _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u)
-        tail = (_ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale, _stream())
-        if obs is None:
-            rc = getattr(self.lib, "alqp_dual_update_" + sfx)(*head, *tail)
-        else:
-            o = self._obs_struct(obs, dims, dt)
-            rc = getattr(self.lib, "alqp_dual_update_obs_" + sfx)(*head, C.byref(o), *tail)
+        o = self._obs_struct(obs, dims, dt) if obs is not None else None
+        rc = getattr(self.lib, "alqp_dual_update_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt),
+            _ptr(uhi, "u_upper", dt), sb_u, st_u, C.byref(o) if o is not None else None, _ptr(lam, "lam", dt),
+            _ptr(rho, "rho", dt), rho_scale, _stream())
         _lib.check(rc, "alqp_dual_update_" + sfx)
+
+    def _backward(self, dims, factor, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, dyn):
+        """alqp_backward_*: `factor` or `workspace` is a device pointer, the other None."""
+        dt = gbar.dtype
+        name = "alqp_backward_" + _dt(gbar)
+        d = _lib.AlqpDims(*dims)
+        dy = _dyn_args(dyn, dims, dt)
+        rc = getattr(self.lib, name)(
+            C.byref(d), factor, workspace, ws_bytes, _ptr(F, "F", dt), _ptr(rho, "rho", dt),
+            _ptr(z_final, "z_final", dt), _ptr(gbar, "gbar", dt), _ptr(q_grad, "q_grad", dt),
+            _ptr(Qd_grad, "Qd_grad", dt), C.byref(dy) if dy is not None else None, _stream())
+        _lib.check(rc, name)
 
     def backward(self, dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad, dyn=None):
         """w = -H^{-1} gbar with the packed factor -> q_grad, Qd_grad; with dyn (a DynGrads) also dF / dc / dx0."""
-        B, T, nx, nu = dims
-        dt = gbar.dtype
-        sfx = _dt(gbar)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        name = ("alqp_backward_" if dyn is None else "alqp_backward_dyn_") + sfx
-        fn = getattr(self.lib, name)
-        extra = [] if dyn is None else _dyn_args(dyn, dims, dt)
-        rc = fn(C.byref(d), _ptr(factor, "factor", dt), _ptr(F, "F", dt), _ptr(rho, "rho", dt),
-                _ptr(z_final, "z_final", dt), _ptr(gbar, "gbar", dt), _ptr(q_grad, "q_grad", dt),
-                _ptr(Qd_grad, "Qd_grad", dt), *extra, _stream())
-        _lib.check(rc, name)
-
+        self._backward(dims, _ptr(factor, "factor", gbar.dtype), None, 0, F, rho, z_final, gbar, q_grad, Qd_grad, dyn)
 
     def new_workspace_nonlin(self, dims, like):
         """A private workspace for nonlinear fused solves: [records | F linearisations]."""
@@ -468,18 +445,9 @@ class HipBackend:
         return torch.empty(need // like.element_size() + 16, dtype=like.dtype, device=like.device)
 
     def backward_ws(self, dims, workspace, F, rho, z_final, gbar, q_grad, Qd_grad, dyn=None):
-        B, T, nx, nu = dims
-        dt = gbar.dtype
-        sfx = _dt(gbar)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        name = ("alqp_backward_ws_" if dyn is None else "alqp_backward_ws_dyn_") + sfx
-        fn = getattr(self.lib, name)
-        extra = [] if dyn is None else _dyn_args(dyn, dims, dt)
-        rc = fn(C.byref(d), _ptr(workspace, "workspace", dt), self.workspace_bytes(*dims, dt),
-                _ptr(F, "F", dt), _ptr(rho, "rho", dt), _ptr(z_final, "z_final", dt),
-                _ptr(gbar, "gbar", dt), _ptr(q_grad, "q_grad", dt), _ptr(Qd_grad, "Qd_grad", dt), *extra, _stream())
-        _lib.check(rc, name)
-
+        """The same with the factor a quad solve or quad Newton step left in `workspace`."""
+        self._backward(dims, None, _ptr(workspace, "workspace", gbar.dtype), self.workspace_bytes(*dims, gbar.dtype),
+                       F, rho, z_final, gbar, q_grad, Qd_grad, dyn)
 
     # ---- interior-point path (csrc/alqp_ipm.hip) -------------------------------------------------
     def _ipm_ws(self, dims, like):
@@ -487,12 +455,7 @@ class HipBackend:
         need = int(self.lib.alqp_ipm_workspace_bytes(C.byref(d), int(like.dtype == torch.float64)))
         if need == 0:
             raise RuntimeError(f"mi_alqp: no interior-point kernel instance for (nx={dims[2]}, nu={dims[3]})")
-        key = ("ipm", like.device, like.dtype)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() * ws.element_size() < need:
-            ws = torch.empty(need // like.element_size() + 16, dtype=like.dtype, device=like.device)
-            self._ws[key] = ws
-        return ws, need
+        return self._scratch(("ipm", like.device, like.dtype), need // like.element_size(), like.dtype, like.device, 16), need
 
     ipm_variant = "auto"   # default kernel of ipm_solve / ipm_backward: a key of _lib.IPM_VARIANTS (include/mi_alqp.h)
 

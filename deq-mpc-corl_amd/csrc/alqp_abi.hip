@@ -54,6 +54,51 @@ static int quad_stagger(int mode, int B, int T, int nx, int nu, int newton_steps
     return (int)(frac * T * period / 1024.0 + 0.5);
 }
 
+// The automatic choice between the team and the quad kernels of the fused solve (alqp_pick_variant, AlqpParams.variant
+// 0): the only copy of the rule. 1 team, 2 quad, 0: no (nx, nu) instance.
+// Quad once the batch fills the chip (16 instances per wavefront, 1024 SIMDs), team below (2-2.4x lower latency at small
+// batches; measured on MI355X at (13,4) T=20: B=128 0.83 vs 1.94 ms, B=4096 2.11 vs 2.08 ms, B=16384 8.2 vs 3.4 ms; (8,2)
+// T=10 crosses near B=5000). The team kernels' time is a step function of the batch - 2048 (fp32) / 1024 (fp64) teams
+// fit the chip at once - and B = 4096 is exactly two / four full rounds: measured at (13,4) T=20 after round 3's
+// team-kernel work, fp32 B = 4096 team 1.83 vs quad 2.00 ms, B = 5120 2.36 vs 2.08; fp64 B = 4096 4.35 vs 4.71, B = 5120
+// 5.42 vs 5.02 (profiles/r03/experiments/README.md).
+template <typename real>
+int pick_variant(const AlqpDims *dims, int flags, long quad_min_batch) {
+    const size_t team_lds = lds_query<real>(dims->nx, dims->nu, dims->T);
+    if (team_lds == 0) return 0;
+    if (flags & ALQP_SAVE_FACTOR) return 1;   // only the team kernels write the packed factor
+    long qmin = quad_min_batch;
+    if (qmin < 0) {
+        // whole-wavefront teams (2n + nx + 1 > 32 rows, e.g. (13,4)): team through B = 4096 (full rounds), quad beyond;
+        // smaller teams share a wavefront and were not re-measured: round 2's rule
+        const bool wave_team = 2 * (dims->nx + dims->nu) + dims->nx + 1 > 32;
+        qmin = wave_team ? 4097 : (sizeof(real) == 8 ? 4608 : 4096);
+    }
+    // long horizons whose factor does not fit the team's LDS image run on the quad kernels at any batch
+    return (dims->B >= qmin || team_lds > kMaxLds) ? 2 : 1;
+}
+
+// The SolveArgs fields that alqp_solve_lin and alqp_solve_nonlin fill alike; F, c, factor, stagger and dyn_h are the
+// caller's. false: ALQP_EXIT_IN_KERNEL without its scratch or together with a skip flag (ALQP_E_BADARG).
+template <typename real>
+bool set_solve(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *x0,
+               const void *u_lo, const void *u_hi, long sb_u, long st_u, void *z, void *lam, void *rho, void *phi,
+               void *rnorm2, int *info, unsigned char *status, SolveArgs<real> &a) {
+    a.B = dims->B; a.T = dims->T;
+    a.al_iter = prm->al_iter; a.max_newton = prm->max_newton; a.n_ls = prm->n_ls; a.flags = prm->flags;
+    a.rho_scale = (real)prm->rho_scale;
+    a.Qd = (const real *)Qd; a.q = (const real *)q; a.x0 = (const real *)x0;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.z = (real *)z; a.lam = (real *)lam; a.rho = (real *)rho; a.phi = (real *)phi;
+    a.rnorm2 = (real *)rnorm2; a.info = info; a.status = status;
+    a.skip = prm->skip_flag;
+    if (prm->flags & ALQP_EXIT_IN_KERNEL) {
+        if (!prm->exit_scratch || prm->skip_flag) return false;
+        a.exit_tol = prm->exit_tol; a.newton_counts = prm->newton_counts; a.exit_scratch = prm->exit_scratch;
+    }
+    return true;
+}
+
 template <typename real>
 int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
                    const void *F, const void *c, const void *x0, const void *u_lo, const void *u_hi,
@@ -64,21 +109,12 @@ int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, 
         return ALQP_E_BADARG;
     if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
     if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
     SolveArgs<real> a = {};
-    a.B = dims->B; a.T = dims->T;
-    a.al_iter = prm->al_iter; a.max_newton = prm->max_newton; a.n_ls = prm->n_ls; a.flags = prm->flags;
-    a.rho_scale = (real)prm->rho_scale;
-    a.Qd = (const real *)Qd; a.q = (const real *)q; a.F = (const real *)F; a.c = (const real *)c;
-    a.x0 = (const real *)x0; a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi;
-    a.sb_u = sb_u; a.st_u = st_u;
-    a.z = (real *)z; a.lam = (real *)lam; a.rho = (real *)rho; a.phi = (real *)phi;
-    a.rnorm2 = (real *)rnorm2; a.info = info; a.status = status; a.factor = (real *)factor_out;
-    a.skip = prm->skip_flag;
+    if (!set_solve(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+        return ALQP_E_BADARG;
+    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
     a.stagger = quad_stagger(prm->quad_stagger, dims->B, dims->T, dims->nx, dims->nu, prm->al_iter * prm->max_newton, sizeof(real) == 8);
-    if (prm->flags & ALQP_EXIT_IN_KERNEL) {
-        if (!prm->exit_scratch || trace || prm->skip_flag) return ALQP_E_BADARG;
-        a.exit_tol = prm->exit_tol; a.newton_counts = prm->newton_counts; a.exit_scratch = prm->exit_scratch;
-    }
     TraceArgs<real> tr = {};
     if (trace) {
         tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
@@ -87,21 +123,10 @@ int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, 
     // variant: 1 = team (factor in LDS), 2 = quad (4 lanes/instance, HBM workspace), 0 = auto
     const size_t need = quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
     int variant = prm->variant;
-    // auto: quad once the batch fills the chip (16 instances per wavefront, 1024 SIMDs), team below
-    // (2-2.4x lower latency at small batches). The team kernels' time is a step function of the batch - 2048 (fp32) /
-    // 1024 (fp64) teams fit the chip at once - and B = 4096 is exactly two / four full rounds: measured at (13,4) T=20
-    // after round 3's team-kernel work, fp32 B = 4096 team 1.83 vs quad 2.00 ms, B = 5120 2.36 vs 2.08; fp64 B = 4096 4.35
-    // vs 4.71, B = 5120 5.42 vs 5.02 (profiles/r03/experiments/README.md).
     if (variant == 0) {
-        const size_t team_lds = lds_query<real>(dims->nx, dims->nu, dims->T);
-        const bool team_fits = team_lds > 0 && team_lds <= kMaxLds;
-        const bool quad_ok = need > 0 && workspace && ws_bytes >= need && !(prm->flags & ALQP_SAVE_FACTOR);
-        // long horizons whose factor does not fit the team's LDS image run on the quad kernels at any batch
-        // whole-wavefront teams (2n + nx + 1 > 32 rows, e.g. (13,4)): team through B = 4096 (full rounds), quad beyond;
-        // smaller teams share a wavefront and were not re-measured: round 2's rule
-        const bool wave_team = 2 * (dims->nx + dims->nu) + dims->nx + 1 > 32;
-        const int qmin = wave_team ? 4097 : (sizeof(real) == 8 ? 4608 : 4096);
-        variant = (quad_ok && (dims->B >= qmin || !team_fits)) ? 2 : 1;
+        variant = pick_variant<real>(dims, prm->flags, -1);
+        if (variant == 0) return ALQP_E_UNSUPPORTED;
+        if (variant == 2 && !(need > 0 && workspace && ws_bytes >= need)) variant = 1;   // no workspace to run quad on
     }
     if (variant == 2) {
         if (prm->flags & ALQP_SAVE_FACTOR) return ALQP_E_UNSUPPORTED;
@@ -135,107 +160,75 @@ int solve_nonlin_impl(const AlqpDims *dims, const AlqpParams *prm, int dyn_id, d
     if (need == 0) return ALQP_E_UNSUPPORTED;
     if (ws_bytes < need) return ALQP_E_BADARG;
     SolveArgs<real> a = {};
-    a.B = dims->B; a.T = dims->T;
-    a.al_iter = prm->al_iter; a.max_newton = prm->max_newton; a.n_ls = prm->n_ls; a.flags = prm->flags;
-    a.rho_scale = (real)prm->rho_scale;
-    a.Qd = (const real *)Qd; a.q = (const real *)q; a.c = nullptr; a.x0 = (const real *)x0;
+    if (!set_solve(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+        return ALQP_E_BADARG;
     a.F = (const real *)((const char *)workspace + quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T));
-    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
-    a.z = (real *)z; a.lam = (real *)lam; a.rho = (real *)rho; a.phi = (real *)phi;
-    a.rnorm2 = (real *)rnorm2; a.info = info; a.status = status; a.factor = nullptr;
-    a.skip = prm->skip_flag;
     a.dyn_h = (real)dyn_h;
-    if (prm->flags & ALQP_EXIT_IN_KERNEL) {
-        if (!prm->exit_scratch || prm->skip_flag) return ALQP_E_BADARG;
-        a.exit_tol = prm->exit_tol; a.newton_counts = prm->newton_counts; a.exit_scratch = prm->exit_scratch;
-    }
     return dispatch_solve_nonlin<real>(dyn_id, dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
+}
+
+// a non-null workspace selects the quad kernels; ALQP_E_* when it cannot hold these dims, else 0
+template <typename real>
+int check_quad_ws(const AlqpDims *dims, size_t ws_bytes) {
+    const size_t need = quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
+    if (need == 0) return ALQP_E_UNSUPPORTED;
+    return ws_bytes < need ? ALQP_E_BADARG : 0;
 }
 
 template <typename real>
 int newton_step_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
                      const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                     const void *u_lo, const void *u_hi, long sb_u, long st_u, void *d_out,
-                     void *g_out, void *factor_out, int *info, void *stream, const AlqpObstacles *obs = nullptr,
-                     void *workspace = nullptr, size_t ws_bytes = 0) {
+                     const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
+                     void *workspace, size_t ws_bytes, void *d_out, void *g_out, void *factor_out, int *info,
+                     void *stream) {
     if (!dims_ok(dims) || !z || !xnext || !F || !x0 || !lam || !rho || !Qd || !q || !u_lo || !u_hi || !d_out)
         return ALQP_E_BADARG;
-    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
     StepArgs<real> a = {};
-    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
-    if (obs) a.no_init = obs->state_estimator;
+    if (!set_obstacles<real>(dims, obs, a)) return ALQP_E_BADARG;
     a.B = dims->B; a.T = dims->T;
     a.z = (const real *)z; a.xnext = (const real *)xnext; a.F = (const real *)F; a.x0 = (const real *)x0;
     a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
     a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
     a.d_out = (real *)d_out; a.g_out = (real *)g_out; a.factor = (real *)factor_out; a.info = info;
-    if (workspace) {   // quad variant: the factor stays in the workspace records (alqp_backward_ws)
+    if (workspace) {   // quad variant: the factor stays in the workspace records (for alqp_backward_*)
         if (factor_out) return ALQP_E_BADARG;
-        const size_t need = quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
-        if (need == 0) return ALQP_E_UNSUPPORTED;
-        if (ws_bytes < need) return ALQP_E_BADARG;
+        if (const int rc = check_quad_ws<real>(dims, ws_bytes)) return rc;
         return dispatch_step_quad<real>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
     }
     return dispatch_step<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
 }
 
-// the dynamics-gradient outputs of alqp_backward_dyn_* / alqp_backward_ws_dyn_* (all null: the plain backward)
-struct BwdDyn {
-    const void *lam = nullptr;
-    long sb_lam = 0;
-    void *dF = nullptr, *dc = nullptr, *dx0 = nullptr;
-};
+// fills what the plain and the DYN backward share and launches: quad kernels on a workspace, team kernels on a factor
 template <typename real, bool DYN>
-void set_bwd(const AlqpDims *dims, const void *factor, const void *F, const void *rho, const void *z_final,
-             const void *gbar, void *q_grad, void *Qd_grad, BwdArgs<real, DYN> &a) {
+int launch_backward(const AlqpDims *dims, const void *factor, void *workspace, const void *F, const void *rho,
+                    const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, BwdArgs<real, DYN> &a,
+                    void *stream) {
     a.B = dims->B; a.T = dims->T;
     a.factor = (const real *)factor; a.F = (const real *)F; a.rho = (const real *)rho;
     a.z_final = (const real *)z_final; a.gbar = (const real *)gbar;
     a.q_grad = (real *)q_grad; a.Qd_grad = (real *)Qd_grad;
-}
-template <typename real>
-bool set_dyn(const AlqpDims *dims, const BwdDyn &d, BwdArgs<real, true> &a) {
-    if (d.dF && (!d.lam || d.sb_lam < (long)(dims->T - 1) * dims->nx)) return false;
-    a.lam = (const real *)d.lam; a.sb_lam = d.sb_lam;
-    a.dF = (real *)d.dF; a.dc = (real *)d.dc; a.dx0 = (real *)d.dx0;
-    return true;
+    if (workspace)
+        return dispatch_backward_quad<real, DYN>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
+    return dispatch_backward<real, DYN>(dims->nx, dims->nu, a, (hipStream_t)stream);
 }
 
 template <typename real>
-int backward_impl(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
-                  const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, void *stream,
-                  const BwdDyn *dyn = nullptr) {
-    if (!dims_ok(dims) || !factor || !F || !rho || !z_final || !gbar || !q_grad || !Qd_grad)
+int backward_impl(const AlqpDims *dims, const void *factor, void *workspace, size_t ws_bytes, const void *F,
+                  const void *rho, const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
+                  const AlqpBwdDyn *dyn, void *stream) {
+    if (!dims_ok(dims) || !factor == !workspace || !F || !rho || !z_final || !gbar || !q_grad || !Qd_grad)
         return ALQP_E_BADARG;
-    if (dyn) {
-        BwdArgs<real, true> a = {};
-        set_bwd(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad, a);
-        if (!set_dyn(dims, *dyn, a)) return ALQP_E_BADARG;
-        return dispatch_backward<real, true>(dims->nx, dims->nu, a, (hipStream_t)stream);
+    if (workspace)
+        if (const int rc = check_quad_ws<real>(dims, ws_bytes)) return rc;
+    if (!dyn) {   // the plain kernels, the kernel arguments they always had
+        BwdArgs<real> a = {};
+        return launch_backward(dims, factor, workspace, F, rho, z_final, gbar, q_grad, Qd_grad, a, stream);
     }
-    BwdArgs<real> a = {};
-    set_bwd(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad, a);
-    return dispatch_backward<real, false>(dims->nx, dims->nu, a, (hipStream_t)stream);
-}
-
-template <typename real>
-int backward_ws_impl(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F, const void *rho,
-                     const void *z_final, const void *gbar, void *q_grad, void *Qd_grad, void *stream,
-                     const BwdDyn *dyn = nullptr) {
-    if (!dims_ok(dims) || !workspace || !F || !rho || !z_final || !gbar || !q_grad || !Qd_grad)
-        return ALQP_E_BADARG;
-    const size_t need = quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
-    if (need == 0) return ALQP_E_UNSUPPORTED;
-    if (ws_bytes < need) return ALQP_E_BADARG;
-    if (dyn) {
-        BwdArgs<real, true> a = {};
-        set_bwd(dims, nullptr, F, rho, z_final, gbar, q_grad, Qd_grad, a);
-        if (!set_dyn(dims, *dyn, a)) return ALQP_E_BADARG;
-        return dispatch_backward_quad<real, true>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
-    }
-    BwdArgs<real> a = {};
-    set_bwd(dims, nullptr, F, rho, z_final, gbar, q_grad, Qd_grad, a);
-    return dispatch_backward_quad<real, false>(dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
+    if (dyn->dF && (!dyn->lam || dyn->sb_lam < (long)(dims->T - 1) * dims->nx)) return ALQP_E_BADARG;
+    BwdArgs<real, true> a = {};
+    a.lam = (const real *)dyn->lam; a.sb_lam = dyn->sb_lam;
+    a.dF = (real *)dyn->dF; a.dc = (real *)dyn->dc; a.dx0 = (real *)dyn->dx0;
+    return launch_backward(dims, factor, workspace, F, rho, z_final, gbar, q_grad, Qd_grad, a, stream);
 }
 
 }  // namespace alqp
@@ -243,7 +236,7 @@ int backward_ws_impl(const AlqpDims *dims, void *workspace, size_t ws_bytes, con
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 11; }
+int alqp_abi_version(void) { return 12; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -293,6 +286,12 @@ int alqp_supported_variant(const AlqpDims *dims, int is_f64, int variant) {
     return 0;
 }
 
+int alqp_pick_variant(const AlqpDims *dims, int is_f64, int flags, long quad_min_batch) {
+    if (!alqp::dims_ok(dims)) return 0;
+    return is_f64 ? alqp::pick_variant<double>(dims, flags, quad_min_batch)
+                  : alqp::pick_variant<float>(dims, flags, quad_min_batch);
+}
+
 int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
     (void)is_f64;
     if (!alqp::dims_ok(dims)) return 0;
@@ -313,82 +312,21 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
     int alqp_newton_step_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
                                const void *x0, const void *lam, const void *rho, const void *Qd,      \
                                const void *q, const void *u_lo, const void *u_hi, long sb_u,          \
-                               long st_u, void *d_out, void *g_out, void *factor_out, int *info,      \
-                               void *stream) {                                                        \
+                               long st_u, const AlqpObstacles *obs, void *workspace, size_t ws_bytes, \
+                               void *d_out, void *g_out, void *factor_out, int *info, void *stream) { \
         return alqp::newton_step_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
-                                            st_u, d_out, g_out, factor_out, info, stream);            \
+                                            st_u, obs, workspace, ws_bytes, d_out, g_out, factor_out, \
+                                            info, stream);                                            \
     }                                                                                                 \
-    int alqp_newton_step_obs_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
-                                   const void *x0, const void *lam, const void *rho, const void *Qd,  \
-                                   const void *q, const void *u_lo, const void *u_hi, long sb_u,      \
-                                   long st_u, const AlqpObstacles *obs, void *d_out, void *g_out,     \
-                                   void *factor_out, int *info, void *stream) {                       \
-        return alqp::newton_step_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
-                                            st_u, d_out, g_out, factor_out, info, stream, obs);       \
-    }                                                                                                 \
-    int alqp_backward_##SFX(const AlqpDims *dims, const void *factor, const void *F, const void *rho, \
-                            const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,       \
+    int alqp_backward_##SFX(const AlqpDims *dims, const void *factor, void *workspace,                \
+                            size_t ws_bytes, const void *F, const void *rho, const void *z_final,     \
+                            const void *gbar, void *q_grad, void *Qd_grad, const AlqpBwdDyn *dyn,     \
                             void *stream) {                                                           \
-        return alqp::backward_impl<REAL>(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad,        \
-                                         stream);                                                     \
+        return alqp::backward_impl<REAL>(dims, factor, workspace, ws_bytes, F, rho, z_final, gbar,    \
+                                         q_grad, Qd_grad, dyn, stream);                               \
     }
 
 ALQP_DEFINE(f32, float)
 ALQP_DEFINE(f64, double)
-
-#define ALQP_DEFINE_STEP_WS(SFX, REAL)                                                                \
-    int alqp_newton_step_ws_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
-                                  const void *x0, const void *lam, const void *rho, const void *Qd,   \
-                                  const void *q, const void *u_lo, const void *u_hi, long sb_u,       \
-                                  long st_u, void *workspace, size_t ws_bytes, void *d_out,           \
-                                  void *g_out, int *info, void *stream) {                             \
-        if (!workspace) return ALQP_E_BADARG;                                                         \
-        return alqp::newton_step_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
-                                            st_u, d_out, g_out, nullptr, info, stream, nullptr,       \
-                                            workspace, ws_bytes);                                     \
-    }                                                                                                 \
-    int alqp_newton_step_ws_obs_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
-                                      const void *x0, const void *lam, const void *rho, const void *Qd, \
-                                      const void *q, const void *u_lo, const void *u_hi, long sb_u,   \
-                                      long st_u, const AlqpObstacles *obs, void *workspace, size_t ws_bytes, \
-                                      void *d_out, void *g_out, int *info, void *stream) {            \
-        if (!workspace) return ALQP_E_BADARG;                                                         \
-        return alqp::newton_step_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
-                                            st_u, d_out, g_out, nullptr, info, stream, obs,           \
-                                            workspace, ws_bytes);                                     \
-    }
-ALQP_DEFINE_STEP_WS(f32, float)
-ALQP_DEFINE_STEP_WS(f64, double)
-
-int alqp_backward_ws_f32(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
-                         const void *rho, const void *z_final, const void *gbar, void *q_grad,
-                         void *Qd_grad, void *stream) {
-    return alqp::backward_ws_impl<float>(dims, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, stream);
-}
-int alqp_backward_ws_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
-                         const void *rho, const void *z_final, const void *gbar, void *q_grad,
-                         void *Qd_grad, void *stream) {
-    return alqp::backward_ws_impl<double>(dims, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, stream);
-}
-
-#define ALQP_DEFINE_BWD_DYN(SFX, REAL)                                                                \
-    int alqp_backward_dyn_##SFX(const AlqpDims *dims, const void *factor, const void *F, const void *rho, \
-                                const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,   \
-                                const void *lam, long sb_lam, void *dF, void *dc, void *dx0,          \
-                                void *stream) {                                                       \
-        const alqp::BwdDyn d = {lam, sb_lam, dF, dc, dx0};                                            \
-        return alqp::backward_impl<REAL>(dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad,        \
-                                         stream, &d);                                                 \
-    }                                                                                                 \
-    int alqp_backward_ws_dyn_##SFX(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F, \
-                                   const void *rho, const void *z_final, const void *gbar,            \
-                                   void *q_grad, void *Qd_grad, const void *lam, long sb_lam,         \
-                                   void *dF, void *dc, void *dx0, void *stream) {                     \
-        const alqp::BwdDyn d = {lam, sb_lam, dF, dc, dx0};                                            \
-        return alqp::backward_ws_impl<REAL>(dims, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, \
-                                            Qd_grad, stream, &d);                                     \
-    }
-ALQP_DEFINE_BWD_DYN(f32, float)
-ALQP_DEFINE_BWD_DYN(f64, double)
 
 }  // extern "C"

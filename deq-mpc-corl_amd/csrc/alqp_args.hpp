@@ -107,9 +107,9 @@ struct StepArgs {
     int no_init;       // state-estimator row set (AlqpObstacles.state_estimator)
 };
 
-// DYN = false: the plain backward (alqp_backward_*), the kernel arguments it always had. DYN = true (alqp_backward_dyn_*)
-// adds the gradients w.r.t. the affine dynamics and the initial state behind them, in a type of its own so that the
-// plain kernels' argument block, and with it their code, stays what it was.
+// DYN = false: the plain backward (alqp_backward_* with dyn = NULL), the kernel arguments it always had. DYN = true (a
+// non-null AlqpBwdDyn) adds the gradients w.r.t. the affine dynamics and the initial state behind them, in a type of
+// its own so that the plain kernels' argument block, and with it their code, stays what it was.
 template <typename real, bool DYN = false>
 struct BwdArgs {
     int B, T;

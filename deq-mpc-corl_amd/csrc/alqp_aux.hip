@@ -2,7 +2,7 @@
 // batch-global exit test; one wavefront per instance) with their C ABI.
 #include <hip/hip_runtime.h>
 
-#include "alqp_launch.hpp"   // dims_ok
+#include "alqp_launch.hpp"   // dims_ok, set_obstacles
 #include "mi_alqp.h"
 
 namespace alqp {
@@ -274,14 +274,12 @@ __global__ void k_exit_test(const double *sumsq, double *ctl, int mode, double t
 template <typename real>
 int merit_impl(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
                const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
-               const void *u_hi, long sb_u, long st_u, void *phi, void *rnorm2, void *stream,
-               const AlqpObstacles *obs = nullptr) {
+               const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs, void *phi, void *rnorm2,
+               void *stream) {
     if (!dims_ok(dims) || K < 1 || !zc || !xnext || !x0 || !lam || !rho || !Qd || !q || !u_lo || !u_hi || !phi)
         return ALQP_E_BADARG;
-    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
     AuxArgs<real> a = {};
-    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
-    if (obs) a.no_init = obs->state_estimator;
+    if (!set_obstacles<real>(dims, obs, a)) return ALQP_E_BADARG;
     a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu; a.K = K;
     a.zc = (const real *)zc; a.xnext = (const real *)xnext; a.x0 = (const real *)x0;
     a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
@@ -300,10 +298,8 @@ int merit_pick_impl(const AlqpDims *dims, int n_ls, const void *d, const void *x
     if (!dims_ok(dims) || n_ls < 1 || n_ls > 20 || !d || !xnext_all || !x0 || !lam || !rho || !Qd || !q || !u_lo ||
         !u_hi || !z || !phi_prev)
         return ALQP_E_BADARG;
-    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
     AuxArgs<real> a = {};
-    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
-    if (obs) a.no_init = obs->state_estimator;
+    if (!set_obstacles<real>(dims, obs, a)) return ALQP_E_BADARG;
     a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu; a.n_ls = n_ls;
     a.d = (const real *)d; a.xnext = (const real *)xnext_all; a.x0 = (const real *)x0;
     a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
@@ -328,13 +324,11 @@ int pick_impl(const AlqpDims *dims, int n_ls, const void *phi, void *phi_prev, c
 
 template <typename real>
 int dual_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *x0, const void *u_lo,
-              const void *u_hi, long sb_u, long st_u, void *lam, void *rho, double rho_scale,
-              void *stream, const AlqpObstacles *obs = nullptr) {
+              const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs, void *lam, void *rho,
+              double rho_scale, void *stream) {
     if (!dims_ok(dims) || !z || !xnext || !x0 || !u_lo || !u_hi || !lam || !rho) return ALQP_E_BADARG;
-    if (obs && (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3)))) return ALQP_E_BADARG;
     AuxArgs<real> a = {};
-    if (obs && obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
-    if (obs) a.no_init = obs->state_estimator;
+    if (!set_obstacles<real>(dims, obs, a)) return ALQP_E_BADARG;
     a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu;
     a.zc = (const real *)z; a.xnext = (const real *)xnext; a.x0 = (const real *)x0;
     a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
@@ -357,16 +351,9 @@ int alqp_exit_test(const double *sumsq, double *ctl, int mode, double tol, void 
     int alqp_merit_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,              \
                          const void *x0, const void *lam, const void *rho, const void *Qd,            \
                          const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,     \
-                         void *phi, void *rnorm2, void *stream) {                                     \
+                         const AlqpObstacles *obs, void *phi, void *rnorm2, void *stream) {           \
         return alqp::merit_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u,      \
-                                      st_u, phi, rnorm2, stream);                                     \
-    }                                                                                                 \
-    int alqp_merit_obs_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,          \
-                             const void *x0, const void *lam, const void *rho, const void *Qd,        \
-                             const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u, \
-                             const AlqpObstacles *obs, void *phi, void *rnorm2, void *stream) {       \
-        return alqp::merit_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u,      \
-                                      st_u, phi, rnorm2, stream, obs);                                \
+                                      st_u, obs, phi, rnorm2, stream);                                \
     }                                                                                                 \
     int alqp_merit_pick_##SFX(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all,   \
                               const void *x0, const void *lam, const void *rho, const void *Qd,       \
@@ -384,16 +371,10 @@ int alqp_exit_test(const double *sumsq, double *ctl, int mode, double tol, void 
     }                                                                                                 \
     int alqp_dual_update_##SFX(const AlqpDims *dims, const void *z, const void *xnext,                \
                                const void *x0, const void *u_lo, const void *u_hi, long sb_u,         \
-                               long st_u, void *lam, void *rho, double rho_scale, void *stream) {     \
-        return alqp::dual_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, lam, rho, rho_scale, \
-                                     stream);                                                         \
-    }                                                                                                 \
-    int alqp_dual_update_obs_##SFX(const AlqpDims *dims, const void *z, const void *xnext,            \
-                                   const void *x0, const void *u_lo, const void *u_hi, long sb_u,     \
-                                   long st_u, const AlqpObstacles *obs, void *lam, void *rho,         \
-                                   double rho_scale, void *stream) {                                  \
-        return alqp::dual_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, lam, rho, rho_scale, \
-                                     stream, obs);                                                    \
+                               long st_u, const AlqpObstacles *obs, void *lam, void *rho,             \
+                               double rho_scale, void *stream) {                                      \
+        return alqp::dual_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, obs, lam, rho,       \
+                                     rho_scale, stream);                                              \
     }
 
 ALQP_DEFINE_AUX(f32, float)

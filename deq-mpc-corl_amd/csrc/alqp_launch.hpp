@@ -41,6 +41,17 @@ int launch_maybe_coop(Fn fn, unsigned grid, size_t lds, hipStream_t stream, A0 a
 
 inline bool dims_ok(const AlqpDims *d) { return d && d->B > 0 && d->T >= 2 && d->nx > 0 && d->nu > 0; }
 
+// The nullable AlqpObstacles of the C ABI -> the obs, nobs, obs_r2, no_init fields, which StepArgs and AuxArgs name alike
+// (`a` zero-initialised). false: ALQP_E_BADARG.
+template <typename real, typename Args>
+inline bool set_obstacles(const AlqpDims *dims, const AlqpObstacles *obs, Args &a) {
+    if (!obs) return true;
+    if (obs->nobs < 0 || (obs->nobs > 0 && (!obs->pos || dims->nx < 3))) return false;
+    if (obs->nobs > 0) { a.obs = (const real *)obs->pos; a.nobs = obs->nobs; a.obs_r2 = (real)(obs->radius * obs->radius); }
+    a.no_init = obs->state_estimator;
+    return true;
+}
+
 // alqp_team.hip
 template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 // ---- backward of the implicit layer, quad variant: the factor is the workspace a previous
 //      quad solve left behind (per-stage lower triangles of L) ---------------------------------
-// DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_ws_dyn_*). w_t is
+// DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_* with an AlqpBwdDyn). w_t is
 // the record's y/d field; a lane owns rows i = q (mod 4) of F_t as in the sweeps and, per own row, forms
 // s_t[i] = w_{t+1}[i] - F_t[i] . w_t from F and w (the record's s group is not relied on) and writes the row of dF_t.
 template <typename real, int NX, int NU, bool DYN = false>

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(64) void k_newton_step(StepArgs<real> a) {
 }
 
 // ---- backward of the implicit layer -------------------------------------------------
-// DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_dyn_*). With
+// DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_* with an AlqpBwdDyn). With
 // w = -H^{-1} gbar in ds, s_t = w_{t+1}[x] - F_t w_t in seq (what backward_sweep leaves there as (J d)_eq) and
 // v_t = the returned lam's dynamics rows: dF_t[i][j] = -v_t[i] w_t[j] - rho s_t[i] z_t[j], dc_t[i] = -rho s_t[i],
 // dx0[i] = -rho w_0[i].

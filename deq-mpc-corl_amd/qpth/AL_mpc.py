@@ -151,8 +151,8 @@ class _ALSolve(torch.autograd.Function):
     at the last executed Newton step, q_grad = w, Q_grad = w * z_final.
 
     Beyond the reference, on the affine (``LinDx``) routes: when ``LinDx.F``, ``LinDx.f`` or ``x0`` requires grad they
-    are the inputs ``dyn = (F, f, x0)`` and get dF, dc, dx0 of include/mi_alqp.h (alqp_backward_dyn_*) out of the same
-    w, with the same approximations (multipliers and active set held fixed, factor of the last executed Newton step);
+    are the inputs ``dyn = (F, f, x0)`` and get dF, dc, dx0 of include/mi_alqp.h (alqp_backward_* with an AlqpBwdDyn) out
+    of the same w, with the same approximations (multipliers and active set held fixed, factor of the last executed Newton step);
     the multipliers in those formulas are the equality rows of the lam the solve returned, cloned here. With a callable
     ``dx`` nothing of this applies: ``x0.grad`` stays None there.
     """

@@ -10,7 +10,7 @@ Which spheres are "nearest" is decided once per rollout from the reference traje
 ``reinitialize`` (:104-109) and shifted by one stage in ``warm_start_initialize`` (:121-127) - host logic,
 mirrored here. The arithmetic (the rank-<=4 Gauss-Newton update of the position corner of H_tt, the
 state-dependent active set, the merit and dual-update terms) is in the HIP kernels behind
-``alqp_newton_step_obs`` / ``alqp_merit_obs`` / ``alqp_dual_update_obs`` (include/mi_alqp.h). The reference
+the ``AlqpObstacles`` argument of ``alqp_newton_step`` / ``alqp_merit`` / ``alqp_dual_update`` (include/mi_alqp.h). The reference
 only reaches this class with PyTorch-coded dynamics (``FlyingCartpole_obstacles``, policies.py:1181), so the
 solve runs in the nonlinear-caller mode: ``dx`` / ``dx_jac`` between launches.
 """

@@ -45,7 +45,7 @@ typedef struct AlqpDims {
     int nu;  /* control dim */
 } AlqpDims;
 
-/* obstacle rows of Obstacle_MPC (documented with alqp_newton_step_obs_* below) */
+/* obstacle rows of Obstacle_MPC (documented under "Obstacle inequalities" below); nullable wherever it is taken */
 typedef struct AlqpObstacles {
     const void *pos;   /* DEVICE [B][T][nobs][3], the real type of the call */
     double radius;
@@ -119,6 +119,10 @@ int alqp_supported(const AlqpDims *dims, int is_f64);
 /* Per variant (AlqpParams.variant): 1 team - additionally the horizon's factor must fit the LDS image;
  * 2 quad - needs alqp_workspace_bytes() of workspace, no LDS. */
 int alqp_supported_variant(const AlqpDims *dims, int is_f64, int variant);
+/* Which kernel alqp_solve_lin's variant 0 resolves to, given a sufficient workspace: 1 team, 2 quad,
+ * 0 when (nx, nu) has no compiled instance. quad_min_batch < 0: the measured table; >= 0: quad from that batch on
+ * (test and experiment override). */
+int alqp_pick_variant(const AlqpDims *dims, int is_f64, int flags, long quad_min_batch);
 /* LDS bytes one workgroup of the fused kernel uses (0 if unsupported). */
 size_t alqp_lds_bytes(const AlqpDims *dims, int is_f64);
 /* QP instances one 64-lane wavefront solves concurrently (team variant). */
@@ -162,42 +166,34 @@ int alqp_solve_lin_f64(const AlqpDims *dims, const AlqpParams *prm, const void *
  * dx_jac(x,u) -> (xnext, F) in PyTorch (al_utils.py:233-248). Replaces
  * merit_grad_hessian (:80-123) + cholesky_ex/cholesky_solve (:510-515).
  *   out: d[B][T][n] = -H^{-1} g, g_out (nullable), factor_out (nullable), info[B]
+ *   obs (nullable): the extra rows of "Obstacle inequalities" below.
+ *   workspace (nullable): NULL runs the team kernel. Non-null selects the quad kernels (16 instances per wavefront; use
+ *   them once the batch fills the chip, B >= 4096): the per-stage factor is streamed through - and left in - `workspace`
+ *   (alqp_workspace_bytes()), where alqp_backward_* finds it for NewtonAL.backward; no packed factor_out then.
  */
 int alqp_newton_step_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
                          const void *x0, const void *lam, const void *rho, const void *Qd,
                          const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                         const AlqpObstacles *obs, void *workspace, size_t ws_bytes,
                          void *d_out, void *g_out, void *factor_out, int *info, void *stream);
 int alqp_newton_step_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
                          const void *x0, const void *lam, const void *rho, const void *Qd,
                          const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                         const AlqpObstacles *obs, void *workspace, size_t ws_bytes,
                          void *d_out, void *g_out, void *factor_out, int *info, void *stream);
 
 /*
- * The same Newton direction by the quad kernels (16 instances per wavefront; use it once the batch fills the
- * chip, B >= 4096): the per-stage factor is streamed through - and left in - `workspace`
- * (alqp_workspace_bytes()), where alqp_backward_ws_* finds it for NewtonAL.backward. No packed factor_out.
- */
-int alqp_newton_step_ws_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
-                            const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                            const void *u_lo, const void *u_hi, long sb_u, long st_u, void *workspace,
-                            size_t ws_bytes, void *d_out, void *g_out, int *info, void *stream);
-int alqp_newton_step_ws_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
-                            const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                            const void *u_lo, const void *u_hi, long sb_u, long st_u, void *workspace,
-                            size_t ws_bytes, void *d_out, void *g_out, int *info, void *stream);
-
-/*
  * Merit of K stacked candidates (al_utils.py:52-77 with the [K,B,T,n] broadcast of
- * :56-70): zc[K][B][T][n], xnext[K][B][T-1][nx] -> phi[K][B], rnorm2[K][B] (nullable).
+ * :56-70): zc[K][B][T][n], xnext[K][B][T-1][nx] -> phi[K][B], rnorm2[K][B] (nullable). obs nullable.
  */
 int alqp_merit_f32(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
                    const void *lam, const void *rho, const void *Qd, const void *q,
-                   const void *u_lo, const void *u_hi, long sb_u, long st_u, void *phi,
-                   void *rnorm2, void *stream);
+                   const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
+                   void *phi, void *rnorm2, void *stream);
 int alqp_merit_f64(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
                    const void *lam, const void *rho, const void *Qd, const void *q,
-                   const void *u_lo, const void *u_hi, long sb_u, long st_u, void *phi,
-                   void *rnorm2, void *stream);
+                   const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
+                   void *phi, void *rnorm2, void *stream);
 
 /*
  * Line-search decision + update (al_utils.py:634-641): first argmin over phi[n_ls][B],
@@ -229,45 +225,28 @@ int alqp_merit_pick_f64(const AlqpDims *dims, int n_ls, const void *d, const voi
 
 /*
  * Dual update + projection + penalty growth (AL_mpc.py:315-317, 325) given
- * xnext = f(x_t,u_t) at the final iterate; lam, rho updated in place.
+ * xnext = f(x_t,u_t) at the final iterate; lam, rho updated in place. obs nullable.
  */
 int alqp_dual_update_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
-                         const void *u_lo, const void *u_hi, long sb_u, long st_u, void *lam,
-                         void *rho, double rho_scale, void *stream);
+                         const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
+                         void *lam, void *rho, double rho_scale, void *stream);
 int alqp_dual_update_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
-                         const void *u_lo, const void *u_hi, long sb_u, long st_u, void *lam,
-                         void *rho, double rho_scale, void *stream);
+                         const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
+                         void *lam, void *rho, double rho_scale, void *stream);
 
 /*
  * Backward of the implicit layer (NewtonAL.backward, al_utils.py:578-615):
  * w = -H^{-1} gbar with the saved factor; q_grad = w, Qd_grad = w * z_final.
- * rho is the penalty the factor was built with.
- */
-int alqp_backward_f32(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
-                      const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
-                      void *stream);
-int alqp_backward_f64(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
-                      const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
-                      void *stream);
-
-/*
- * Same backward pass, with the factor taken from the workspace a quad-variant
- * alqp_solve_lin_* call left behind (the caller must have kept that workspace untouched:
- * give such solves a dedicated workspace). The workspace's y/d slots are overwritten.
- */
-int alqp_backward_ws_f32(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
-                         const void *rho, const void *z_final, const void *gbar, void *q_grad,
-                         void *Qd_grad, void *stream);
-int alqp_backward_ws_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
-                         const void *rho, const void *z_final, const void *gbar, void *q_grad,
-                         void *Qd_grad, void *stream);
-
-/*
- * The same two backward passes, which also return the gradients w.r.t. the affine dynamics x_{t+1} = F_t z_t + c_t
- * and the initial state (the reference has no such gradient). With w = -H^{-1} gbar as above, rho[b] the penalty the
- * factor was built with (that of the last executed Newton step: the rho the solve returned / rho_scale once a dual
- * update has grown it), v_t the dynamics rows t nx + i of the multipliers the solve RETURNED (after the dual update
- * that ends an AL iteration they hold lam + rho r(z_final) on the equality rows) and
+ * rho is the penalty the factor was built with. Exactly one of `factor` and `workspace` is non-null:
+ *   factor     the packed factor_out of the team kernels;
+ *   workspace  the workspace a quad-variant alqp_solve_lin_* / alqp_newton_step_* call left behind (the caller must have
+ *              kept it untouched: give such solves a dedicated workspace). Its y/d slots are overwritten.
+ *
+ * dyn (nullable; NULL runs the plain kernels): also return the gradients w.r.t. the affine dynamics
+ * x_{t+1} = F_t z_t + c_t and the initial state (the reference has no such gradient). With w = -H^{-1} gbar as above,
+ * rho[b] the penalty the factor was built with (that of the last executed Newton step: the rho the solve returned /
+ * rho_scale once a dual update has grown it), v_t the dynamics rows t nx + i of the multipliers the solve RETURNED (after
+ * the dual update that ends an AL iteration they hold lam + rho r(z_final) on the equality rows) and
  * s_t = w_{t+1}[0:nx] - F_t w_t:
  *     dF [b][t][i][j] = -v_t[i] w_t[j] - rho s_t[i] z_final_t[j]      [B][T-1][nx][n]
  *     dc [b][t][i]    = -rho s_t[i]                                   [B][T-1][nx]
@@ -277,22 +256,18 @@ int alqp_backward_ws_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes,
  * entries are read; only dF needs it. dF, dc, dx0 are nullable each (a null output is not computed);
  * ALQP_E_BADARG when dF is given without lam or with sb_lam < (T-1) nx. q_grad / Qd_grad are those of the plain call.
  */
-int alqp_backward_dyn_f32(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
-                          const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
-                          const void *lam, long sb_lam, void *dF, void *dc, void *dx0, void *stream);
-int alqp_backward_dyn_f64(const AlqpDims *dims, const void *factor, const void *F, const void *rho,
-                          const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
-                          const void *lam, long sb_lam, void *dF, void *dc, void *dx0, void *stream);
-int alqp_backward_ws_dyn_f32(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
-                             const void *rho, const void *z_final, const void *gbar, void *q_grad,
-                             void *Qd_grad, const void *lam, long sb_lam, void *dF, void *dc, void *dx0,
-                             void *stream);
-int alqp_backward_ws_dyn_f64(const AlqpDims *dims, void *workspace, size_t ws_bytes, const void *F,
-                             const void *rho, const void *z_final, const void *gbar, void *q_grad,
-                             void *Qd_grad, const void *lam, long sb_lam, void *dF, void *dc, void *dx0,
-                             void *stream);
+typedef struct AlqpBwdDyn {
+    const void *lam;
+    long sb_lam;
+    void *dF, *dc, *dx0;
+} AlqpBwdDyn;
+int alqp_backward_f32(const AlqpDims *dims, const void *factor, void *workspace, size_t ws_bytes, const void *F,
+                      const void *rho, const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
+                      const AlqpBwdDyn *dyn, void *stream);
+int alqp_backward_f64(const AlqpDims *dims, const void *factor, void *workspace, size_t ws_bytes, const void *F,
+                      const void *rho, const void *z_final, const void *gbar, void *q_grad, void *Qd_grad,
+                      const AlqpBwdDyn *dyn, void *stream);
 
-/* Library/ABI version, bumped when a signature changes. */
 /*
  * The reference leaves its Newton loop on a BATCH-GLOBAL test (al_utils.py:486,551-564):
  * new = ||r_+||_F over the whole batch; stop when new < tol or |old - new| / new < tol.
@@ -366,42 +341,10 @@ int alqp_solve_nonlin_f64(const AlqpDims *dims, const AlqpParams *prm, int dyn_i
  * j < nu upper, j < 2 nu lower, then obstacle j - 2 nu (the reference's stage-major order, al_utils.py:376).
  * The Newton step gets the rank-<=nobs Gauss-Newton update 4 rho (p - o_k)(p - o_k)' of the position corner
  * of H_tt for the rows with c_k >= 0 and the gradient term (lam_k + rho max(c_k, 0)) (-2)(p - o_k).
- * These are the nonlinear-caller building blocks with obstacles (the reference only reaches Obstacle_MPC
- * with PyTorch-coded dynamics); arguments as their plain twins. nx >= 3 required.
+ * AlqpObstacles is a nullable argument of alqp_newton_step_* (team and quad kernels; the reference only reaches
+ * Obstacle_MPC with PyTorch-coded dynamics), alqp_merit_*, alqp_merit_pick_* and alqp_dual_update_*. ALQP_E_BADARG when
+ * nobs < 0, or nobs > 0 with a null pos or nx < 3.
  */
-
-/* The quad-variant Newton step (alqp_newton_step_ws: 16 instances per wavefront, factor left in the workspace records for
- * alqp_backward_ws) with the same extra rows: what Obstacle_MPC and the state-estimator variant run at B >= 4096. */
-int alqp_newton_step_ws_obs_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
-                                const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                                const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
-                                void *workspace, size_t ws_bytes, void *d_out, void *g_out, int *info, void *stream);
-int alqp_newton_step_ws_obs_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
-                                const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                                const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
-                                void *workspace, size_t ws_bytes, void *d_out, void *g_out, int *info, void *stream);
-int alqp_newton_step_obs_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
-                             const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                             const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
-                             void *d_out, void *g_out, void *factor_out, int *info, void *stream);
-int alqp_newton_step_obs_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
-                             const void *x0, const void *lam, const void *rho, const void *Qd, const void *q,
-                             const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
-                             void *d_out, void *g_out, void *factor_out, int *info, void *stream);
-int alqp_merit_obs_f32(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
-                       const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
-                       const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs, void *phi, void *rnorm2,
-                       void *stream);
-int alqp_merit_obs_f64(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
-                       const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
-                       const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs, void *phi, void *rnorm2,
-                       void *stream);
-int alqp_dual_update_obs_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
-                             const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
-                             void *lam, void *rho, double rho_scale, void *stream);
-int alqp_dual_update_obs_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
-                             const void *u_lo, const void *u_hi, long sb_u, long st_u, const AlqpObstacles *obs,
-                             void *lam, void *rho, double rho_scale, void *stream);
 
 /*
  * ---- Interior-point QP solve (the `--solver_type ip` path) -------------------------------------------
@@ -506,6 +449,7 @@ int alqp_dyn_rexquadrotor_f64(long K, const AlqpRigidParams *p, const void *x, c
 int alqp_dyn_flyingcartpole_f32(long K, const AlqpRigidParams *p, const void *x, const void *u, double h, void *xnext, void *F, void *stream);
 int alqp_dyn_flyingcartpole_f64(long K, const AlqpRigidParams *p, const void *x, const void *u, double h, void *xnext, void *F, void *stream);
 
+/* Library/ABI version, bumped when a signature changes. */
 int alqp_abi_version(void);
 
 #ifdef __cplusplus

@@ -2,7 +2,7 @@
 
 With w = -H^{-1} gbar (H: Hessian of the last executed Newton step, rho: the penalty it was built with), v_t the
 dynamics rows of the multipliers the solve RETURNED and s_t = w_{t+1}[0:nx] - F_t w_t (include/mi_alqp.h,
-alqp_backward_dyn_*):
+alqp_backward_* with an AlqpBwdDyn):
 
     dF_t[i][j] = -v_t[i] w_t[j] - rho s_t[i] z_final,t[j]      dc_t[i] = -rho s_t[i]      dx0[i] = -rho w_0[i]
 

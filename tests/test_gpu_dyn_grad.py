@@ -1,6 +1,7 @@
 """Gradients w.r.t. the affine dynamics (dF, dc) and the initial state (dx0) out of the two backward kernels
-(alqp_backward_dyn_* / k_backward<DYN>, alqp_backward_ws_dyn_* / k_backward_quad<DYN>) against the float64 oracle:
-w from orc.backward, then the three formulas of tests/test_dyn_grad_cpu.dyn_grads (pinned there by finite differences).
+(alqp_backward_* with an AlqpBwdDyn: k_backward<DYN> on a packed factor, k_backward_quad<DYN> on a workspace) against
+the float64 oracle: w from orc.backward, then the three formulas of tests/test_dyn_grad_cpu.dyn_grads (pinned there by
+finite differences).
 
 Step route, as test_gpu_quad_backward_ws.py: one Newton step leaves the factor of H at (z, lam, rho) - in the workspace
 records (quad) or packed (team) - so the comparison sees only the backward pass and its epilogue. End to end: MPC with
@@ -138,19 +139,19 @@ def test_dyn_outputs_are_nullable_and_leave_plain_gradients_alone(nx, nu, dtype,
 
 
 def test_dF_without_lam_is_refused():
-    """alqp_backward_dyn_*: ALQP_E_BADARG when lam is null while dF is not - checked on the host before any launch, so no
-    device is needed for the refusal itself."""
+    """alqp_backward_* with an AlqpBwdDyn: ALQP_E_BADARG when lam is null while dF is not - checked on the host before any
+    launch, so no device is needed for the refusal itself. Once on the factor route, once on the workspace route."""
     from deq_mpc_corl_amd import _lib
     import ctypes as C
     lib = _lib.load()
     d = _lib.AlqpDims(4, 5, 4, 2)
     one = C.c_void_p(64)   # never dereferenced: the call is refused first
+    dyn = _lib.AlqpBwdDyn(None, 0, 64, None, None)   # dF without lam
     for sfx in ("f32", "f64"):
-        rc = getattr(lib, "alqp_backward_dyn_" + sfx)(C.byref(d), one, one, one, one, one, one, one, None, 0, one, None,
-                                                      None, None)
+        fn = getattr(lib, "alqp_backward_" + sfx)
+        rc = fn(C.byref(d), one, None, 0, one, one, one, one, one, one, C.byref(dyn), None)
         assert rc == -1   # ALQP_E_BADARG
-        rc = getattr(lib, "alqp_backward_ws_dyn_" + sfx)(C.byref(d), one, 1 << 40, one, one, one, one, one, one, None, 0,
-                                                         one, None, None, None)
+        rc = fn(C.byref(d), None, one, 1 << 40, one, one, one, one, one, one, C.byref(dyn), None)
         assert rc == -1
 
 

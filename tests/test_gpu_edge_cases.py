@@ -308,8 +308,8 @@ def test_long_horizon_beyond_team_lds_runs_on_quad_at_small_batch():
 
 @pytest.mark.gpu
 def test_quad_stagger_changes_timing_only():
-    """alqp_set_quad_stagger: the start offset between a CU's wavefronts must not change a single bit of the
-    results (B = 16384 fills the SIMDs, so the automatic rule is active)."""
+    """AlqpParams.quad_stagger / HipBackend.set_quad_stagger: the start offset between a CU's wavefronts must not change
+    a single bit of the results (B = 16384 fills the SIMDs, so the automatic rule is active)."""
     from deq_mpc_corl_amd.backend import default_backend
     from deq_mpc_corl_amd.problems import synthetic_problem
     be = default_backend()

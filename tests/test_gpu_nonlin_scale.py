@@ -1,5 +1,5 @@
 """Nonlinear-caller mode at scale (what the reference's torch-coded environments hit, al_utils.py:233-265,
-618-642): the quad-variant Newton direction (alqp_newton_step_ws) and the one-launch line search
+618-642): the quad-variant Newton direction (alqp_newton_step with a workspace) and the one-launch line search
 (alqp_merit_pick) against the kernels they replace at large batches, against the oracle, and end to end
 through the drop-in MPC."""
 import numpy as np
@@ -155,7 +155,7 @@ def test_nonlinear_caller_mode_quad_route_equals_team_route(with_grad):
 @pytest.mark.parametrize("rows", ["obstacles", "state_estimator"])
 def test_newton_step_quad_with_extra_rows_equals_team(dims, dtype, tol, rows):
     """Obstacle rows (Obstacle_MPC, al_utils.py:313-323, 351-388) and the state-estimator row set on the quad step
-    kernel (alqp_newton_step_ws_obs) against the team step kernel that the reference fixtures pin
+    kernel (alqp_newton_step with a workspace and obs) against the team step kernel that the reference fixtures pin
     (tests/test_obstacles_golden.py, test_state_estimator_golden.py): ragged batches and the B = 4096 the class switches at."""
     from deq_mpc_corl_amd.backend import default_backend
     be = default_backend()

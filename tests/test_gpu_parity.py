@@ -397,7 +397,7 @@ def test_variants_agree_at_headline_size():
 @pytest.mark.parametrize("exit_mode", ["fixed", "reference"])
 def test_backward_quad_workspace_equals_team_factor(exit_mode, dtype):
     """Gradients w.r.t. q and diag(Q) through the two backward routes - the quad solve's
-    workspace as factor (alqp_backward_ws) and the team kernel's packed factor (alqp_backward) -
+    workspace as factor (alqp_backward with a workspace) and the team kernel's packed factor (alqp_backward) -
     agree on a (13,4) batch; both implement NewtonAL.backward (al_utils.py:578-615). In fp32 the quad
     records are interleaved in instance pairs (B = 37: the last pair is half used)."""
     from deq_mpc_corl_amd import MPC, AffineDynamics, QuadCost, synthetic_problem
@@ -438,7 +438,7 @@ def test_backward_quad_workspace_equals_team_factor(exit_mode, dtype):
         x, u, _ = mpc(p.x0, cost, dyn, dyn.jac, x_init=p.z0[..., :nx].clone(), u_init=p.z0[..., nx:].clone())
         ((x * wx).sum() + (u * wu).sum()).backward()
         if name == "quad":
-            assert calls, "the quad route did not run alqp_backward_ws"
+            assert calls, "the quad route did not run backward_ws"
         grads[name] = (q.grad.clone(), Qd.grad.clone(), x.detach().clone())
     sq = float(grads["team"][0].abs().max())
     eq = float((grads["quad"][0] - grads["team"][0]).abs().max()) / sq

@@ -1,4 +1,4 @@
-"""Backward through the quad workspace records (alqp_backward_ws / k_backward_quad) against a float64 reference, on
+"""Backward through the quad workspace records (alqp_backward on a workspace / k_backward_quad) against a float64 reference, on
 every compiled (nx, nu) and both dtypes. The backward pass reads the factor (L chunks) and the y / d field of every
 record; in fp32 those records are interleaved in pairs of instances (QCfg::IL = 2), so an odd B leaves the last pair
 half used and puts a single real instance into the last wavefront.

@@ -6,7 +6,7 @@
   * drop-in level: `deq_mpc_corl_amd.qpth.AL_mpc_custom.Obstacle_MPC` - nearest-sphere selection in
     reinitialize / warm_start_initialize, Newton-step counts, per-AL-iteration lamda (incl. the obstacle
     rows) and rho, x, u, gradients - on the CPU with the TEST-ONLY oracle backend and on the MI355X through
-    alqp_newton_step_obs / alqp_merit_obs / alqp_dual_update_obs (`-m gpu`).
+    alqp_newton_step / alqp_merit / alqp_dual_update with an AlqpObstacles (`-m gpu`).
 """
 from types import SimpleNamespace
 
@@ -132,7 +132,7 @@ def test_obstacle_mpc_host_logic_cpu(name):
 
 
 def _hip_backend(route):
-    """route "quad": every Newton direction through the quad step kernel (alqp_newton_step_ws_obs: what the class takes by
+    """route "quad": every Newton direction through the quad step kernel (alqp_newton_step with a workspace and obs: what the class takes by
     itself from B = 4096 on), the factor in its workspace records for backward_ws; "team": the small-batch default."""
     from deq_mpc_corl_amd.backend import HipBackend
     be = HipBackend()

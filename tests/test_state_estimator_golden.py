@@ -94,7 +94,7 @@ def test_state_estimator_host_logic_cpu(name):
 @pytest.mark.parametrize("name", SE)
 @pytest.mark.parametrize("route", ["team", "quad"])
 def test_state_estimator_hip(name, route):
-    """route "quad": the state-estimator row set on the quad step kernel (alqp_newton_step_ws_obs, what B >= 4096 takes)."""
+    """route "quad": the state-estimator row set on the quad step kernel (alqp_newton_step with a workspace and obs, what B >= 4096 takes)."""
     from deq_mpc_corl_amd.backend import HipBackend
     be = HipBackend()
     if route == "quad":
