@@ -1124,6 +1124,64 @@ struct Quad {
         if constexpr (C::PHI0_FWD) { if (phi0) *phi0 = qsum(mdist); }
     }
 
+    // ---- triangular solves with a stage's factor on OWN elements -------------------------
+    // Lane q holds element 4m + q of an n-vector in slot m and row 4m + q of Hh in its own registers, so the owner of
+    // a row updates it without fetching anything; one quad broadcast per step carries the finished element to the
+    // other lanes. Lanes of slot m that may work at column j: lo <= q < hi. Rows on or above the diagonal of a 4 x 4
+    // diagonal block hold whatever the forward sweep left there, and the lanes of the last slot without a row hold a
+    // copy of lane 0's words: both are kept out with a select (a product with zero would let a NaN through).
+    __host__ __device__ static constexpr int lane_lo(int m, int j) { return m == (j >> 2) ? (j & 3) + 1 : 0; }
+    __device__ __forceinline__ bool in_lanes(int lo, int hi) const {
+        return lo == 0 ? q < hi : (hi == 4 ? q >= lo : (q >= lo && q < hi));
+    }
+    // u <- Lh^{-1} u, column form (Lh[k][j] = Hh[k][j] / p_j, 1 / p_j on the diagonal): the owner of u_j scales it,
+    // every row below takes its update. The same operations on the same operands as on replicated vectors.
+    // PRECONDITION ON THE CALLER: in the last slot the lanes without a row (q >= NLAST) are not masked here; on return
+    // u[SY - 1] of those lanes is arbitrary (accumulated from the copy of lane 0's words). A caller may read u only
+    // through the owner of an element (qbv from lane k & 3, k < N) or must clear those lanes first, as solve_forward
+    // does before its store; backward() feeds them only into ltsolve_own, which reads y through the owner.
+    __device__ __forceinline__ void lsolve_own(const real (&H)[HT], real (&u)[SY]) const {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int mj = j >> 2;
+            const real wj = qbv(u[mj] * H[C::hidx(mj, j)], j);
+#pragma unroll
+            for (int m = mj; m < SH; ++m) {
+                const int lo = lane_lo(m, j);
+                if (lo >= C::lanes_of(m)) continue;
+                const real v = fma_(-H[C::hidx(m, j)], wj, u[m]);
+                u[m] = lo == 0 ? v : (q >= lo ? v : u[m]);
+            }
+        }
+    }
+    // d <- Lh^{-T} D^{-1} y, dot form: d_i = (y_i - sum_{k>i} Hh[k][i] d_k) / p_i, every lane summing over its own rows
+    // k > i; the owner finishes d_i and broadcasts it. d: own elements (0 where a lane has none), rep: the same vector
+    // on every lane. Of y only the owner's copy of each element is read. (Other forms of this loop that were measured:
+    // profiles/r08/README.md.)
+    __device__ __forceinline__ void ltsolve_own(const real (&H)[HT], const real (&y)[SY], real (&d)[SY], real (&rep)[N]) const {
+#pragma unroll
+        for (int m = 0; m < SY; ++m) d[m] = 0;
+#pragma unroll
+        for (int i = N - 1; i >= 0; --i) {
+            const int mi = i >> 2;
+            real p = 0;
+            bool any = false;
+#pragma unroll
+            for (int m = mi; m < SH; ++m) {
+                const int lo = lane_lo(m, i), hi = C::lanes_of(m);
+                if (lo >= hi) continue;
+                const real h = (lo == 0 && hi == 4) ? H[C::hidx(m, i)] : (in_lanes(lo, hi) ? H[C::hidx(m, i)] : real(0));
+                p = any ? fma_(h, d[m], p) : h * d[m];
+                any = true;
+            }
+            real r = y[mi];
+            if (any) r -= qsum(p);
+            const real di = qbv(r * H[C::hidx(mi, i)], i);
+            rep[i] = di;
+            d[mi] = (q == (i & 3)) ? di : d[mi];
+        }
+    }
+
     // ---- backward sweep ---------------------------------------------------------------
     // LS: also accumulate the merit of the 20 line-search candidates z + 2^-k d while d_t and
     // s_t = (J d)_t are in registers (algebra: merit_candidates below; the sum runs over the
@@ -1140,9 +1198,9 @@ struct Quad {
         for (int k = 0; k < 20; ++k) acc[k] = 0;
 #pragma unroll
         for (int s = 0; s < SW; ++s) rvT[s] = lvT[s] = 0;
-        real dxn[NX];
+        real dxs[SW];   // own x rows of d_{t+1}, 0 where a lane has none
 #pragma unroll
-        for (int j = 0; j < NX; ++j) dxn[j] = 0;
+        for (int s = 0; s < SW; ++s) dxs[s] = 0;
         for (int t = T - 1; t >= 0; --t) {
             const bool dyn = t < T - 1;
             real *rp = recp(t);
@@ -1162,9 +1220,6 @@ struct Quad {
                 }
             real yo[SY];
             ld_own_n(rp + C::oY, yo);
-            real Y[N];
-#pragma unroll
-            for (int j = 0; j < N; ++j) Y[j] = qbv(yo[j >> 2], j);
             WT W = wpanel();
             load_F_rows(dyn ? t : (T > 1 ? T - 2 : 0), W);  // same batch as the record loads
             real zz[SY], QQ[SY], qq[SY], rv[SW], lv[SW];
@@ -1180,12 +1235,6 @@ struct Quad {
                 ld_own_x(rp + C::oLE, lv);
             }
             ALQP_STAMP(4);  // backward: exposed load latency
-            real dxs[SW];
-#pragma unroll
-            for (int s = 0; s < SW; ++s)
-                dxs[s] = sel4(dxn[4 * s], (4 * s + 1 < NX) ? dxn[(4 * s + 1 < NX) ? 4 * s + 1 : 0] : real(0),
-                              (4 * s + 2 < NX) ? dxn[(4 * s + 2 < NX) ? 4 * s + 2 : 0] : real(0),
-                              (4 * s + 3 < NX) ? dxn[(4 * s + 3 < NX) ? 4 * s + 3 : 0] : real(0), q);
             if (dyn) {
                 // v = F_t' dx_{t+1}
                 real vv[N];
@@ -1196,27 +1245,18 @@ struct Quad {
                     for (int s = 0; s < SW; ++s) p = fma_(W[s][j], dxs[s], p);
                     vv[j] = qsum(p);
                 }
-                // u = Lh^{-1} v  (Lh[k][j] = Hh[k][j] / p_j)
+                // u = Lh^{-1} v, rhs = y + rho u
+                real uo[SY];
+                own_of<N, SY>(vv, uo);
+                lsolve_own(H, uo);
 #pragma unroll
-                for (int j = 0; j < N; ++j) {
-                    const real wj = vv[j] * qbv(H[C::hidx(j >> 2, j)], j);
-#pragma unroll
-                    for (int k = j + 1; k < N; ++k) vv[k] = fma_(-qbv(H[C::hidx(k >> 2, j)], k), wj, vv[k]);
-                }
-#pragma unroll
-                for (int j = 0; j < N; ++j) Y[j] = fma_(rho, vv[j], Y[j]);
+                for (int m = 0; m < SY; ++m) yo[m] = fma_(rho, uo[m], yo[m]);
             }
-            // d = Lh^{-T} D^{-1} rhs: d_i = (rhs_i - sum_{k>i} Hh[k][i] d_k) / p_i
-#pragma unroll
-            for (int i = N - 1; i >= 0; --i) {
-                const real di = Y[i] * qbv(H[C::hidx(i >> 2, i)], i);
-                Y[i] = di;
-#pragma unroll
-                for (int j = 0; j < i; ++j) Y[j] = fma_(-qbv(H[C::hidx(i >> 2, j)], i), di, Y[j]);
-            }
+            // d = Lh^{-T} D^{-1} rhs: own elements for the stores, the line search and the next stage, Y on every lane
+            // for s = dx_{t+1} - W d
+            real down[SY], Y[N];
+            ltsolve_own(H, yo, down, Y);
             if (active) {
-                real down[SY];
-                own_of<N, SY>(Y, down);
                 if (d_ext) st_own_ext<N>(d_ext + t * N, down);
                 else st_own_n(rp + C::oY, down);
             }
@@ -1240,10 +1280,7 @@ struct Quad {
                 for (int m = 0; m < SY; ++m) {
                     const int j = 4 * m + q;
                     const real ok = (4 * m + 3 < N || j < N) ? real(1) : real(0);
-                    const real dj = sel4(Y[4 * m], (4 * m + 1 < N) ? Y[(4 * m + 1 < N) ? 4 * m + 1 : 0] : real(0),
-                                         (4 * m + 2 < N) ? Y[(4 * m + 2 < N) ? 4 * m + 2 : 0] : real(0),
-                                         (4 * m + 3 < N) ? Y[(4 * m + 3 < N) ? 4 * m + 3 : 0] : real(0), q);
-                    const real z = zz[m], d = dj * ok, Qv = QQ[m] * ok, qv = qq[m] * ok;
+                    const real z = zz[m], d = down[m], Qv = QQ[m] * ok, qv = qq[m] * ok;
                     c0 = fma_(fma_(real(0.5) * Qv, z, qv), z, c0);
                     c1 = fma_(fma_(Qv, z, qv), d, c1);
                     c2 = fma_(real(0.5) * Qv * d, d, c2);
@@ -1285,24 +1322,17 @@ struct Quad {
                 }
             }
 #pragma unroll
-            for (int j = 0; j < NX; ++j) dxn[j] = Y[j];
+            for (int s = 0; s < SW; ++s) dxs[s] = (4 * s + 3 < NX || 4 * s + q < NX) ? down[s] : real(0);
             ALQP_STAMP(5);  // backward: solves + stores
         }
         // initial-state rows: s = d_0[x]
-        if (active && !d_ext) {
-            real so[SW];
-            own_of<NX, SW>(dxn, so);
-            st_own_x(recp(T - 1) + C::oS, so);
-        }
+        if (active && !d_ext) st_own_x(recp(T - 1) + C::oS, dxs);
         if constexpr (LS) {
 #pragma unroll
             for (int s = 0; s < SW; ++s) {
                 const int r = 4 * s + q;
                 const real ok = (4 * s + 3 < NX || r < NX) ? real(1) : real(0);
-                const real sj = sel4(dxn[4 * s], (4 * s + 1 < NX) ? dxn[(4 * s + 1 < NX) ? 4 * s + 1 : 0] : real(0),
-                                     (4 * s + 2 < NX) ? dxn[(4 * s + 2 < NX) ? 4 * s + 2 : 0] : real(0),
-                                     (4 * s + 3 < NX) ? dxn[(4 * s + 3 < NX) ? 4 * s + 3 : 0] : real(0), q);
-                const real rr = rvT[s] * ok, ss = sj * ok, lm = lvT[s] * ok;
+                const real rr = rvT[s] * ok, ss = dxs[s], lm = lvT[s] * ok;
                 c0 = fma_(fma_(real(0.5) * rho, rr, lm), rr, c0);
                 c1 = fma_(fma_(rho, rr, lm), ss, c1);
                 c2 = fma_(real(0.5) * rho * ss, ss, c2);
@@ -1338,46 +1368,29 @@ struct Quad {
                     gld4(lchunk(rp, s, c, ql), H[C::hidx(s, 4 * c)],
                          H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
                 }
-            real Y[N];
-            gload<N>(gbar + t * N, Y);
+            real yo[SY];
+            ld_own_ext<N, SY>(gbar + t * N, yo);
             WT W = wpanel();
             load_F_rows(t > 0 ? t - 1 : 0, W);
 #pragma unroll
-            for (int j = 0; j < N; ++j) Y[j] = -Y[j];
+            for (int m = 0; m < SY; ++m) yo[m] = -yo[m];
             if (t > 0) {
-                real cpl[SW];
+                // the x rows take rho (F_{t-1} e)[row]: row 4s + q is this lane's own
 #pragma unroll
                 for (int s = 0; s < SW; ++s) {
                     real p = 0;
 #pragma unroll
                     for (int k = 0; k < N; ++k) p = fma_(W[s][k], e[k], p);
-                    cpl[s] = p;
+                    yo[s] = (4 * s + 3 < NX || 4 * s + q < NX) ? fma_(rho, p, yo[s]) : yo[s];
                 }
-#pragma unroll
-                for (int j = 0; j < NX; ++j) Y[j] = fma_(rho, qbv(cpl[j >> 2], j), Y[j]);
             }
             // u = Lh^{-1} rhs
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const real yj = Y[j] * qbv(H[C::hidx(j >> 2, j)], j);
-#pragma unroll
-                for (int k = j + 1; k < N; ++k) Y[k] = fma_(-qbv(H[C::hidx(k >> 2, j)], k), yj, Y[k]);
-            }
-            if (active) {
-                real yo[SY];
-                own_of<N, SY>(Y, yo);
-                st_own_n(rp + C::oY, yo);
-            }
+            lsolve_own(H, yo);
+            if constexpr (C::NLAST < 4) yo[SY - 1] = q < C::NLAST ? yo[SY - 1] : real(0);   // lsolve_own's precondition
+            if (active) st_own_n(rp + C::oY, yo);
             // e = Lh^{-T} D^{-1} u for the coupling of the next stage
-#pragma unroll
-            for (int j = 0; j < N; ++j) e[j] = Y[j];
-#pragma unroll
-            for (int i = N - 1; i >= 0; --i) {
-                const real ei = e[i] * qbv(H[C::hidx(i >> 2, i)], i);
-                e[i] = ei;
-#pragma unroll
-                for (int j = 0; j < i; ++j) e[j] = fma_(-qbv(H[C::hidx(i >> 2, j)], i), ei, e[j]);
-            }
+            real eo[SY];
+            ltsolve_own(H, yo, eo, e);
         }
     }
 
