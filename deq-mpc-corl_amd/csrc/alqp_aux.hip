@@ -208,7 +208,8 @@ __global__ __launch_bounds__(64) void k_pick(AuxArgs<real> a) {
     }
     const real prev = a.phi_prev[b];
     const bool acc = best < prev;
-    const real alpha = acc ? real(1) / real(1 << kbest) : real(0);
+    // 2^-kbest in `real`: n_ls has no upper limit here, an integer shift would be undefined from kbest = 31 on
+    const real alpha = acc ? ldexp(real(1), -kbest) : real(0);
     real *z = a.z + (size_t)b * Tn;
     const real *d = a.d + (size_t)b * Tn;
     if (acc)

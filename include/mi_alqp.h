@@ -199,6 +199,7 @@ int alqp_merit_f64(const AlqpDims *dims, int K, const void *zc, const void *xnex
  * Line-search decision + update (al_utils.py:634-641): first argmin over phi[n_ls][B],
  * accept iff strictly below phi_prev; z <- accept ? z + 2^-k d : z (in place);
  * phi_prev <- phi_min regardless (al_utils.py:569). k_out/accept_out nullable.
+ * Any n_ls >= 1: 2^-k is formed in the solve's precision for every k (zero once it underflows).
  */
 int alqp_linesearch_pick_f32(const AlqpDims *dims, int n_ls, const void *phi, void *phi_prev,
                              const void *d, void *z, int *k_out, int *accept_out, void *stream);

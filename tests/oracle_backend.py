@@ -189,9 +189,10 @@ class OracleBackend:
         s = _sfx(z)
         lo, hi = _bounds(ulo, uhi, sb_u, st_u, B, T, nu)
         with self._obs(s, obs):
-            ll, rr = orc.dual_update(s, _n(z), _n(xnext), _n(x0), lo, hi, _n(lam), _n(rho))
+            ll, _ = orc.dual_update(s, _n(z), _n(xnext), _n(x0), lo, hi, _n(lam), _n(rho))
         lam.copy_(torch.from_numpy(ll))
-        rho.copy_(torch.from_numpy(rr))
+        # the oracle grows rho by the reference's constant 10; the entry point by real(rho_scale), in `real` (k_dual)
+        rho.mul_(torch.tensor(rho_scale, dtype=rho.dtype))
 
     def backward(self, dims, factor, F, rho, z_final, gbar, q_grad, Qd_grad):
         B, T, nx, nu = dims

@@ -104,9 +104,41 @@ def test_merit_pick_equals_merit_then_pick(dims, dtype, with_obs):
         want = torch.where(a1.bool(), rn2s.gather(0, k1.long().unsqueeze(0)).squeeze(0), torch.full_like(rn2, -1.0))
         assert torch.allclose(rn2, want, rtol=1e-12)
     else:
-        same = (k1 == k2) & (a1 == a2)
-        assert float(same.float().mean()) > 0.9          # fp32 near-ties between neighbouring candidates
-        assert torch.allclose(z1[same], z2[same], atol=1e-6)
+        # fp32: neighbouring candidates can be closer than the rounding of their merits, so the two routes need not
+        # agree on k. Each route must pick a minimiser of the fp64 oracle's merits (of z + 2^-k d formed in fp64 from
+        # the same inputs) up to its own rounding, tests/aux_cases.py::gamma_merit, and take the oracle's decision.
+        from contextlib import nullcontext
+        from oracle import oracle_py as orc
+        from tests import aux_cases as ac
+        n64 = lambda t: t.detach().cpu().double().numpy()
+        z64, d64, nobs = n64(z), n64(d), 4 if with_obs else 0
+        lo, hi = (np.ascontiguousarray(np.broadcast_to(n64(v), (B, T, nu))) for v in (p.u_lo, p.u_hi))
+        ctx = orc.obstacles("f64", n64(obs[0]), obs[1]) if with_obs else nullcontext()
+        phi_ref, A = [], []
+        for k in range(20):
+            zk, xk = z64 + 2.0 ** -k * d64, n64(xnc[k])
+            with ctx:
+                phi_ref.append(orc.merit("f64", zk, xk, n64(p.x0), n64(lam), n64(rho), n64(p.Qd), n64(p.q), lo, hi)[0])
+            A.append(ac.merit_magnitude(zk, xk, n64(p.x0), n64(lam), n64(rho), n64(p.Qd), n64(p.q), lo, hi,
+                                        obs_pos=n64(obs[0]) if with_obs else None, radius=obs[1] if with_obs else 0.0,
+                                        zmag=np.abs(z64) + 2.0 ** -k * np.abs(d64)).A)
+        phi_ref, A = np.stack(phi_ref), np.stack(A)
+        tol = ac.gamma_merit(T, nx, nu, nobs, cand=True) * 2.0 ** -24 * A
+        tol_b = tol.max(0)
+        assert (np.abs(n64(phi_all) - phi_ref) <= tol).all() and (np.abs(n64(phis) - phi_ref) <= tol).all()
+        acc_ref = phi_ref.min(0) < n64(phi_prev)
+        bi = np.arange(B)
+        for kk, aa, zz, pp, ph in ((k1, a1, z1, pp1, phis), (k2, a2, z2, pp2, phi_all)):
+            kg, ag = kk.cpu().numpy(), aa.cpu().numpy() > 0
+            assert (phi_ref[kg, bi] - phi_ref.min(0) <= 2 * tol_b).all()
+            assert np.array_equal(ag, acc_ref)
+            assert torch.equal(pp, ph.gather(0, kk.long().unsqueeze(0)).squeeze(0))
+            want = z64 + 2.0 ** -kg[:, None, None] * d64
+            assert (np.abs(n64(zz) - want)[ag] <= 2.0 ** -24 * (np.abs(z64) + np.abs(d64))[ag]).all()
+            assert torch.equal(zz[~aa.bool()], z[~aa.bool()])
+        want2 = np.where(n64(a2) > 0, n64(rn2s)[k2.cpu().numpy(), bi], -1.0)
+        assert np.array_equal(n64(rn2) == -1.0, n64(a2) == 0)
+        assert np.allclose(n64(rn2), want2, rtol=2e-5, atol=0)
 
 
 @pytest.mark.parametrize("with_grad", [False, True])
