@@ -139,6 +139,31 @@ int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, 
     return dispatch_solve<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
 }
 
+// Dense stage cost: the team kernel only (no quad kernel reads a full C), so no workspace and variant 0 / 1 alike.
+template <typename real>
+int solve_lin_dense_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Cm, const void *q, const void *F,
+                         const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                         void *z, void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
+                         void *factor_out, const AlqpTrace *trace, void *stream) {
+    if (!dims_ok(dims) || !prm || !Cm || !q || !F || !c || !x0 || !u_lo || !u_hi || !z || !lam || !rho || !phi)
+        return ALQP_E_BADARG;
+    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
+    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
+    DenseSolveArgs<real> a = {};
+    if (!set_solve<real>(dims, prm, nullptr, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+        return ALQP_E_BADARG;
+    a.C = (const real *)Cm;
+    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
+    TraceArgs<real> tr = {};
+    if (trace) {
+        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
+        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
+    }
+    return dispatch_solve_dense<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
+}
+
 // nonlinear fused solve: workspace = [records | F linearisations [B][T-1][nx][n]]
 template <typename real>
 size_t nonlin_ws_bytes(int nx, int nu, int B, int T) {
@@ -236,7 +261,7 @@ int backward_impl(const AlqpDims *dims, const void *factor, void *workspace, siz
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 12; }
+int alqp_abi_version(void) { return 13; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -308,6 +333,16 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
         return alqp::solve_lin_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, \
                                           rho, phi, rnorm2, info, status, factor_out, trace,          \
                                           workspace, ws_bytes, stream);                               \
+    }                                                                                                 \
+    int alqp_solve_lin_dense_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *C,        \
+                                   const void *q, const void *F, const void *c, const void *x0,       \
+                                   const void *u_lo, const void *u_hi, long sb_u, long st_u, void *z, \
+                                   void *lam, void *rho, void *phi, void *rnorm2, int *info,          \
+                                   unsigned char *status, void *factor_out, const AlqpTrace *trace,   \
+                                   void *stream) {                                                    \
+        return alqp::solve_lin_dense_impl<REAL>(dims, prm, C, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, \
+                                                lam, rho, phi, rnorm2, info, status, factor_out,      \
+                                                trace, stream);                                       \
     }                                                                                                 \
     int alqp_newton_step_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
                                const void *x0, const void *lam, const void *rho, const void *Qd,      \

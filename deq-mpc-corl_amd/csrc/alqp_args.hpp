@@ -27,6 +27,13 @@ struct SolveArgs {
     double *exit_scratch;  // arrival counter, then [2][gridDim.x] per-workgroup partial sums (ping-pong), then a time-out flag
 };
 
+// The dense-cost fused solve (k_solve_lin_dense): the stage cost's full matrices behind the plain arguments, in a type of
+// its own so that SolveArgs, and with it the plain kernels' argument block, stays what it was. Qd is unused.
+template <typename real>
+struct DenseSolveArgs : SolveArgs<real> {
+    const real *C;   // [B][T][n][n] row-major, symmetric
+};
+
 // sum of one value per workgroup over the whole (cooperatively launched) grid, the same bits in every lane of every
 // workgroup: partials in workgroup order, 64 interleaved chains, xor butterfly. Every workgroup must call it.
 __device__ inline double grid_sum_ordered(double block_val, double *scratch, int &phase) {

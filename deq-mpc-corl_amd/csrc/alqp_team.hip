@@ -1,6 +1,6 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
-#ifdef ALQP_BWD_DYN_UNIT
+#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -25,8 +25,18 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // `s_or_b64 exec` that re-enables the lanes - the store then runs with EXEC = 0 and the reload returns stale scratch. Seen once
 // (k_solve_lin<double,12,4,true,2>: the zs base offset spilled after the `for (e = li; e < T*N; e += G)` load loop, every row
 // of the returned z one repeated value); the uncapped builds have no spills (checked per kernel: tools/spill_report.py).
+// The dense-cost unit (-DALQP_DENSE_UNIT) compiles this same body as k_solve_lin_dense: the stage cost's full C_t at a.C,
+// [B][T][N][N], in place of a.Qd; uncapped builds only. Two headers over one body, rather than a shared device function:
+// called through one, every plain instantiation came out with different register allocation.
+#ifdef ALQP_DENSE_UNIT
+template <typename real, int NX, int NU, bool TRACE>
+__global__ __launch_bounds__(64, 1) void k_solve_lin_dense(DenseSolveArgs<real> a, TraceArgs<real> tr) {
+    constexpr bool DENSE = true;
+#else
 template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
 __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceArgs<real> tr) {
+    constexpr bool DENSE = false;
+#endif
     if (a.skip && *a.skip != 0.0) return;  // block-uniform, before any barrier
     using C = Cfg<real, NX, NU>;
     constexpr int G = C::G, N = C::N;
@@ -38,13 +48,17 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     const int b = active ? b_raw : a.B - 1;
     const int T = a.T, M = C::M(T), neq = T * NX;
 
-    Team<real, NX, NU> tm;
+    Team<real, NX, NU, DENSE> tm;
 #ifdef ALQP_PHASE_TIMING
     for (int i = 0; i < 8; ++i) tm.tacc[i] = 0;
     tm.stamp(-1);
 #endif
     tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
+#ifdef ALQP_DENSE_UNIT
+    tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
+#else
     tm.gQd = a.Qd + (size_t)b * T * N;
+#endif
     tm.gq = a.q + (size_t)b * T * N;
     tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
     tm.gc = a.c + (size_t)b * (T - 1) * NX;
@@ -342,6 +356,7 @@ inline long team_simds() {   // SIMDs of the device (4 per CU)
     return n;
 }
 
+#ifndef ALQP_DENSE_UNIT
 template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
@@ -362,6 +377,16 @@ int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream) {
     });
 }
 
+#else
+template <typename real>
+int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
+        return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
+    });
+}
+#endif
+
 template <typename real, bool DYN>
 int dispatch_backward(int nx, int nu, const BwdArgs<real, DYN> &a, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
@@ -376,7 +401,11 @@ size_t lds_query(int nx, int nu, int T) {
 
 // The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
-#ifndef ALQP_BWD_DYN_UNIT
+// So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT).
+#if defined(ALQP_DENSE_UNIT)
+template int dispatch_solve_dense<float>(int, int, const DenseSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
+template int dispatch_solve_dense<double>(int, int, const DenseSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+#elif !defined(ALQP_BWD_DYN_UNIT)
 template int dispatch_solve<float>(int, int, const SolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve<double>(int, int, const SolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 template int dispatch_step<float>(int, int, const StepArgs<float> &, hipStream_t);

@@ -194,7 +194,11 @@ __device__ inline void wave_sync() { asm volatile("" ::: "memory"); }
 
 // ---- the team -------------------------------------------------------------------
 
-template <typename real, int NX, int NU>
+// DENSE (k_solve_lin_dense only): the stage cost is 1/2 z_t' C_t z_t + q_t' z_t with a full symmetric C_t read from gC
+// ([T][N][N] row-major, this instance) instead of diag(gQd). H lane hi keeps row hi of C_t in registers, fetched a stage
+// ahead like F; the LDS image is the same. Every DENSE statement sits behind `if constexpr`, so the DENSE = false
+// instantiations compile to the code they had before the flag existed.
+template <typename real, int NX, int NU, bool DENSE = false>
 struct Team {
     using C = Cfg<real, NX, NU>;
     static constexpr int N = C::N, NP = C::NP, NXP = C::NXP, G = C::G, XT = C::XT;
@@ -220,6 +224,7 @@ struct Team {
     int nobs;
     real obs_r2;
     bool no_init;       // state-estimator variant: no initial-state rows, zero cost gradient on u (al_utils_se.py:186-200, 300-310)
+    const real *gC;     // DENSE only: this instance's C, [T][N][N] (global memory)
 
 #ifdef ALQP_PHASE_TIMING
     // debug build only (tools/team_timing.py): cycles per phase of the team kernel. Buckets: 0 stage inputs + gradient,
@@ -267,6 +272,7 @@ struct Team {
         info = 0;
         gxnext = nullptr;
         gobs = nullptr; nobs = 0; obs_r2 = 0; no_init = false;
+        gC = nullptr;
         // constant zero rows / pads of the SYRK operands
         for (int e = li; e < RB * NXP; e += G) Ft[e] = 0;
         for (int e = li; e < RB * NP; e += G) Sb[e] = 0;
@@ -295,6 +301,12 @@ struct Team {
             int e = li + i * G;
             if (e < NX * N) Fs[e] = buf[i];
         }
+    }
+    // DENSE: row hi of C_t (H lanes; rows are N words long, so only 4-byte alignment holds)
+    __device__ void fetch_C(int t, real (&row)[N]) const {
+        const real *Cg = gC + ((size_t)t * N + hi) * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) row[k] = isH ? Cg[k] : real(0);
     }
     __device__ void load_F(int t) {
         real buf[FCH];
@@ -340,7 +352,9 @@ struct Team {
         // initial-state residual (eq row block T-1), al_utils.py:274
         if (li < NX) req[(T - 1) * NX + li] = no_init ? real(0) : zs[li] - gx0[li];
         fetch_F(0, fbuf);
-        real Qn = isH ? gQd[hi] : real(0), qn = isH ? gq[hi] : real(0);
+        real Qn = isH ? (DENSE ? real(0) : gQd[hi]) : real(0), qn = isH ? gq[hi] : real(0);
+        real crn[DENSE ? N : 1], cr[DENSE ? N : 1];   // DENSE: row hi of C_{t+1} in flight, of C_t in use
+        if constexpr (DENSE) fetch_C(0, crn);
         real cn = isW ? (gxnext ? gxnext[wr] : gc[wr]) : real(0);
         // multipliers this lane needs at stage t (global memory, prefetched a stage ahead):
         //   x rows: lam of the eq row that pins x_t (init row for t = 0, dynamics row t-1)
@@ -356,6 +370,10 @@ struct Team {
         for (int t = 0; t < T; ++t) {
             const bool dyn = t < T - 1;
             const real Qv = Qn, qv = qn, cv = cn, la = lan, lb = lbn;
+            if constexpr (DENSE) {
+#pragma unroll
+                for (int k = 0; k < N; ++k) cr[k] = crn[k];
+            }
             if (dyn) stash_F(fbuf);
             wave_sync();
             // ---- own F row (W lanes) / F column (H lanes) into registers
@@ -376,7 +394,12 @@ struct Team {
             wave_sync();
             // ---- prefetch the next stage's inputs (they stay in flight during this stage)
             if (t + 2 < T) fetch_F(t + 1, fbuf);
-            if (t + 1 < T && isH) { Qn = gQd[(t + 1) * N + hi]; qn = gq[(t + 1) * N + hi]; }
+            if constexpr (DENSE) {
+                if (t + 1 < T) fetch_C(t + 1, crn);
+                if (t + 1 < T && isH) qn = gq[(t + 1) * N + hi];
+            } else {
+                if (t + 1 < T && isH) { Qn = gQd[(t + 1) * N + hi]; qn = gq[(t + 1) * N + hi]; }
+            }
             if (t + 2 < T && isW) {
                 cn = gxnext ? gxnext[(t + 1) * NX + wr] : gc[(t + 1) * NX + wr];
                 lan = lams[(t + 1) * NX + wr];
@@ -405,8 +428,20 @@ struct Team {
             real hob[3] = {0, 0, 0};   // obstacle rows: rho J_k'J_k entries (hi, 0..2) of the active rows
             if (isH) {
                 real zv = zs[t * N + hi];
-                real g = fma_(Qv, zv, qv);
-                D = Qv;
+                real g;
+                if constexpr (DENSE) {
+                    // (C_t z_t)[hi] + q_t[hi]; all of row hi goes into Hs below, D keeps the penalty terms only
+                    real zr[N];   // operands first, products after (see backward_sweep)
+#pragma unroll
+                    for (int k = 0; k < N; ++k) zr[k] = zs[t * N + k];
+                    __builtin_amdgcn_sched_barrier(0);
+                    g = qv;
+#pragma unroll
+                    for (int k = 0; k < N; ++k) g = fma_(cr[k], zr[k], g);
+                } else {
+                    g = fma_(Qv, zv, qv);
+                    D = Qv;
+                }
                 if (hi < NX) {
                     int row = (t == 0) ? (T - 1) * NX + hi : (t - 1) * NX + hi;
                     if (!(no_init && t == 0)) {
@@ -493,6 +528,18 @@ struct Team {
             TSTAMP(1);
             // ---- diagonal of H_tt on top of the SYRK result (same lane order: in-order LDS)
             if (isH) Hs[hi * HP + hi] += D;
+            if constexpr (DENSE) {
+                // row hi of C_t on top of row hi of H_tt (the panel reads the lower triangle; C_t is symmetric)
+                if (isH) {
+#pragma unroll
+                    for (int k4 = 0; k4 < NP; k4 += 4) {
+                        real h4[4];
+                        ld4(Hs + hi * HP + k4, h4);
+                        st4(Hs + hi * HP + k4, h4[0] + cr[k4], k4 + 1 < N ? h4[1] + cr[k4 + 1] : h4[1],
+                            k4 + 2 < N ? h4[2] + cr[k4 + 2] : h4[2], k4 + 3 < N ? h4[3] + cr[k4 + 3] : h4[3]);
+                    }
+                }
+            }
             if constexpr (NX >= 3) {
                 if (nobs > 0 && isH && hi < 3) {
                     Hs[hi * HP + 0] += hob[0]; Hs[hi * HP + 1] += hob[1]; Hs[hi * HP + 2] += hob[2];
@@ -709,11 +756,28 @@ struct Team {
         real c0 = 0, c1 = 0, c2 = 0;
         for (int e = li; e < T * N; e += G) {
             real z = zs[e], d = at_z ? real(0) : ds[e];
-            real Qv = gQd[e], qv = gq[e];
-            real gz = fma_(Qv, z, qv);
-            c0 = fma_(fma_(real(0.5) * Qv, z, qv), z, c0);
-            c1 = fma_(gz, d, c1);
-            c2 = fma_(real(0.5) * Qv * d, d, c2);
+            if constexpr (DENSE) {
+                // e = (t, i): (C_t z_t)_i and (C_t d_t)_i from row i of C_t (global) and zs / ds (LDS)
+                const real *Cg = gC + (size_t)e * N;
+                const int t0 = (e / N) * N;
+                real Cz = 0, Cd = 0;
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    const real cv = Cg[k];
+                    Cz = fma_(cv, zs[t0 + k], Cz);
+                    Cd = fma_(cv, at_z ? real(0) : ds[t0 + k], Cd);
+                }
+                const real qv = gq[e];
+                c0 = fma_(fma_(real(0.5), Cz, qv), z, c0);
+                c1 = fma_(Cz + qv, d, c1);
+                c2 = fma_(real(0.5) * Cd, d, c2);
+            } else {
+                real Qv = gQd[e], qv = gq[e];
+                real gz = fma_(Qv, z, qv);
+                c0 = fma_(fma_(real(0.5) * Qv, z, qv), z, c0);
+                c1 = fma_(gz, d, c1);
+                c2 = fma_(real(0.5) * Qv * d, d, c2);
+            }
         }
         for (int e = li; e < neq; e += G) {
             real r = req[e], sv = at_z ? real(0) : seq[e], lm = lams[e];

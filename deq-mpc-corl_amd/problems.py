@@ -75,6 +75,21 @@ def synthetic_problem(B, T, nx, nu, seed=0, dtype=torch.float64, active=False,
     return Problem(B, T, nx, nu, Qd, q, F, c, x0, u_lo, u_hi, xref.clone(), xref)
 
 
+def synthetic_dense_cost(p, seed=0):
+    """A dense stage cost for the synthetic problem `p`: -> (C [B,T,n,n], q [B,T,n]) in p's dtype and device, with
+    C = 0.3 A A' / n + diag(5 on states, 1e-3 on controls), A ~ N(0,1) drawn in fp64 on the CPU generator, and
+    q = -C xref. C is symmetric positive definite with off-diagonals of order 1; with ``active=True`` most controls
+    still end on a bound."""
+    n = p.nx + p.nu
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    A = torch.randn(p.B, p.T, n, n, generator=g, dtype=torch.float64)
+    C = 0.3 * (A @ A.transpose(-1, -2)) / n + torch.diag(torch.tensor([5.0] * p.nx + [1e-3] * p.nu, dtype=torch.float64))
+    C = 0.5 * (C + C.transpose(-1, -2))
+    q = -torch.einsum("btij,btj->bti", C, p.xref.detach().cpu().to(torch.float64))
+    return C.to(p.Qd.dtype).to(p.Qd.device).contiguous(), q.to(p.Qd.dtype).to(p.Qd.device).contiguous()
+
+
 class AffineDynamics:
     """``dx``/``dx_jac`` callables for time-varying affine dynamics.
 

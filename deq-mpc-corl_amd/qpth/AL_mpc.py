@@ -74,6 +74,7 @@ class _Launcher:
     def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once):
         self.be, self.st, self.dims, self.Qd, self.q, self.F, self.c = be, st, dims, Qd, q, F, c
         self.linearize_once = linearize_once   # F, c are the linearisation frozen at the warm start
+        self.dense = Qd.dim() == 4             # Qd is all of C [B,T,n,n] (MPC(diag_cost=False)): solve_lin_dense, team kernel
         self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
         self.has_backward_ws = hasattr(be, "backward_ws")
         self.has_solve_nonlin = hasattr(be, "solve_nonlin")
@@ -98,8 +99,9 @@ class _Launcher:
 
     def lin(self, info=True, **kw):
         st = self.st
-        return self.be.solve_lin(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, st.z, st.lam, st.rho,
-                                 self.phi, info=self.info if info else None, n_ls=N_LS, **self._out, **kw)
+        solve = self.be.solve_lin_dense if self.dense else self.be.solve_lin
+        return solve(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, st.z, st.lam, st.rho,
+                     self.phi, info=self.info if info else None, n_ls=N_LS, **self._out, **kw)
 
     def lin_tracked(self, flags, private=True, **kw):
         """solve_lin with the ALQP_WS_PRIMED bookkeeping. `primed` is the workspace whose records hold THIS solve's
@@ -110,7 +112,7 @@ class _Launcher:
         dtype, and nothing between this solve's launches (dx / dx_jac included) may make it grow its cache."""
         on = self.private_kw if private else {}
         wsx = on.get("workspace")
-        if wsx is None and self.cached_ws is not None:
+        if wsx is None and self.cached_ws is not None and not self.dense:   # (no quad kernel reads a dense cost)
             if self._cached is None:
                 self._cached = self.cached_ws(self.dims, self.st.z)[0]
             wsx = self._cached
@@ -155,6 +157,10 @@ class _ALSolve(torch.autograd.Function):
     of the same w, with the same approximations (multipliers and active set held fixed, factor of the last executed Newton step);
     the multipliers in those formulas are the equality rows of the lam the solve returned, cloned here. With a callable
     ``dx`` nothing of this applies: ``x0.grad`` stays None there.
+
+    Dense cost (``MPC(diag_cost=False)``): ``Qd`` is all of C, [B,T,n,n] and symmetric, and its gradient is
+    0.5 (w z_final' + z_final w') per stage, formed here from the unchanged backward call's w = q_grad (its diagonal is
+    the Qd_grad of the diagonal case).
     """
 
     @staticmethod
@@ -167,6 +173,7 @@ class _ALSolve(torch.autograd.Function):
         ctx.has_factor = saved is not None
         ctx.n_dyn = len(dyn)
         ctx.dyn_dtypes = tuple(t.dtype for t in dyn)
+        ctx.dense = Qd.dim() == 4
         if saved is not None:
             kind, factor, F_last, rho_last = saved
             ctx.factor_kind = kind  # "packed" (team kernels) or "workspace" (quad solve's workspace)
@@ -198,6 +205,9 @@ class _ALSolve(torch.autograd.Function):
             ctx.mpc.backend.backward_ws(ctx.dims, factor, F_last, rho_last, z_final, gbar, q_grad, Qd_grad, **kw)
         else:
             ctx.mpc.backend.backward(ctx.dims, factor, F_last, rho_last, z_final, gbar, q_grad, Qd_grad, **kw)
+        if ctx.dense:
+            wz = q_grad.unsqueeze(-1) * z_final.unsqueeze(-2)
+            Qd_grad = 0.5 * (wz + wz.transpose(-1, -2))
         if not ctx.n_dyn:
             return Qd_grad, q_grad, None
         if not outs:
@@ -213,7 +223,10 @@ class MPC(Module):
         min_{x,u} sum_t 1/2 tau_t' C_t tau_t + c_t' tau_t     tau_t = [x_t; u_t]
         s.t.      x_{t+1} = f(x_t, u_t),  x_0 = x_init,  u_lower <= u <= u_upper
 
-    Differentiable w.r.t. the cost (diag C and c, as the reference). With affine dynamics given as ``LinDx(F, f)`` (F
+    Differentiable w.r.t. the cost (diag C and c, as the reference). ``diag_cost=False``: C_t is a full matrix (cross
+    terms, a Riccati terminal cost, a rotated frame); its symmetric part enters the solve and the gradient reaches all of
+    C. That exists for affine dynamics given as ``LinDx`` only (the fused team kernel), not with a callable ``dx``,
+    ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``. With affine dynamics given as ``LinDx(F, f)`` (F
     [B,T-1,nx,n], f [B,T-1,nx], no broadcast over the batch) the solve is also differentiable w.r.t. ``F``, ``f`` and
     ``x0`` (see ``_ALSolve``); not on the streaming route (``NotImplementedError``). With a callable ``dx`` there are
     no such gradients: ``x0.grad`` stays ``None``.
@@ -230,9 +243,12 @@ class MPC(Module):
         super().__init__()
         if (u_lower is None) != (u_upper is None) or u_lower is None:
             raise ValueError("MPC: u_lower and u_upper are both required (AL_mpc.py:145,152)")
-        if add_goal_constraint or ineqG is not None or not diag_cost:
-            raise NotImplementedError("goal constraints / general inequalities / dense cost are "
+        if add_goal_constraint or ineqG is not None:
+            raise NotImplementedError("goal constraints / general inequalities are "
                                       "not reachable from Tracking_MPC and are not built")
+        if not diag_cost and state_estimator:
+            raise NotImplementedError("MPC: diag_cost=False with state_estimator: that variant runs on the "
+                                      "nonlinear-caller kernels, which read diag(C)")
         if exit_mode not in ("reference", "fixed"):
             raise ValueError("exit_mode must be 'reference' or 'fixed'")
         self.dtype = dtype
@@ -244,7 +260,7 @@ class MPC(Module):
         self.al_iter = al_iter
         self.verbose = verbose
         self.n_batch = n_batch
-        self.diag_cost = True
+        self.diag_cost = bool(diag_cost)
         self.linearize_once = False
         self.recompute_Qq = False
         # state_estimator=True (AL_mpc.py:179-199 -> qpth/al_utils_se.py): the controls are GIVEN and only the
@@ -345,8 +361,11 @@ class MPC(Module):
 
     def get_cost(self, cost):
         xu = self.get_xu()
-        Qd = cost.C.diagonal(dim1=-2, dim2=-1)
         f = cost.f.sum(dim=-1) if cost.f is not None else 0.0
+        if not self.diag_cost:
+            Cxu = (cost.C * xu.unsqueeze(-2)).sum(-1)   # (type-promoting like the diagonal form: xu is float32)
+            return (0.5 * (xu * Cxu).sum(-1) + (cost.c * xu).sum(-1)).sum(dim=-1) + f
+        Qd = cost.C.diagonal(dim1=-2, dim2=-1)
         return (0.5 * (xu * Qd * xu).sum(-1) + (cost.c * xu).sum(-1)).sum(dim=-1) + f
 
     def rollout(self, x, actions, dynamics):
@@ -390,7 +409,7 @@ class MPC(Module):
             x = expand(self.x_init)
         x = x.type_as(x0.data)
 
-        Qd = cost.C.diagonal(dim1=-2, dim2=-1)
+        Qd = cost.C.diagonal(dim1=-2, dim2=-1) if self.diag_cost else self._sym(cost.C)
         x, u, status = self._al_solve(x, u, dx, dx_jac, x0, Qd, cost.c, bool(self.warm_starting))
         self.x_init = x.detach().clone()
         self.u_init = u.detach().clone()
@@ -402,14 +421,29 @@ class MPC(Module):
             self.lamda_prev = lamda_init
         if rho_init is not None:
             self.rho_prev = rho_init
-        return self._al_solve(x, u, dx, dx_jac, x0, cost.C, cost.c, False)
+        return self._al_solve(x, u, dx, dx_jac, x0, self._cost_C(cost), cost.c, False)
 
     def al_solve_stream(self, x, u, dx, dx_jac, x0, cost, lamda_init=None, rho_init=None):
         if lamda_init is not None:
             self.lamda_prev = lamda_init
         if rho_init is not None:
             self.rho_prev = rho_init
-        return self._al_solve(x, u, dx, dx_jac, x0, cost.C, cost.c, True)
+        return self._al_solve(x, u, dx, dx_jac, x0, self._cost_C(cost), cost.c, True)
+
+    @staticmethod
+    def _sym(Cm):
+        """The symmetric part of C [B,T,n,n]: the quadratic form only sees it, and the dense kernel reads whole rows.
+        Under autograd, so that the gradient reaches both halves of C."""
+        return 0.5 * (Cm + Cm.transpose(-1, -2))
+
+    def _cost_C(self, cost):
+        """cost.C as al_solve / al_solve_stream hand it on: diag(C) [B,T,n] as given, or with diag_cost=False all of C
+        [B,T,n,n], symmetrised."""
+        if self.diag_cost:
+            return cost.C
+        if cost.C.dim() != 4:
+            raise ValueError(f"MPC(diag_cost=False): cost.C must be [B,T,n,n], got {tuple(cost.C.shape)}")
+        return self._sym(cost.C)
 
     # -- internals -------------------------------------------------------------------
     def _obs_kwargs(self, dtype, device):
@@ -749,6 +783,18 @@ class MPC(Module):
         if not be.supported(B, T, nx, nu, dt):
             raise RuntimeError(f"mi_alqp: no kernel instance for (nx={nx}, nu={nu}, T={T}, {dt}); "
                                "add it to ALQP_FOR_EACH_DIMS in csrc/alqp_dims.hpp")
+        if not self.diag_cost:
+            # the dense cost lives in the fused team kernel alone (alqp_solve_lin_dense): everything that reaches the
+            # nonlinear-caller kernels or a compiled-in model reads diag(C)
+            if self._has_extra_rows():
+                raise NotImplementedError("MPC: diag_cost=False with obstacle rows / state_estimator: those run on the "
+                                          "nonlinear-caller kernels, which read diag(C)")
+            if self.linearize_once:
+                raise NotImplementedError("MPC: diag_cost=False with linearize_once: the frozen-linearisation route "
+                                          "evaluates merit and dual update with kernels that read diag(C)")
+            if st.lin is None:
+                raise NotImplementedError("MPC: diag_cost=False needs affine dynamics given as LinDx(F, f): the "
+                                          "nonlinear-caller kernels and the compiled-in models read diag(C)")
         if self.state_estimator:
             # cost gradient on the states only (al_utils_se.py:300-310) while the Hessian keeps diag(Q) on the
             # controls (:66-68): the kernels' `state_estimator` flag. Their merit still counts the controls' cost
@@ -783,7 +829,7 @@ class MPC(Module):
             c = st.lin[1].detach().to(device=dev, dtype=dt).contiguous()
         L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once)
         # the quad kernels take the obstacle / state-estimator rows too, so their factor can stay in the records
-        use_qws = need_grad and L.has_backward_ws and B >= L.quad_min_batch
+        use_qws = need_grad and L.has_backward_ws and B >= L.quad_min_batch and not L.dense   # dense: packed factor
         if use_qws:
             L.qws = be.new_workspace(dims, st.z)
             L.private_kw = dict(workspace=L.qws, variant="quad")

@@ -31,6 +31,9 @@ class Obstacle_MPC(MPC):
                          n_batch, linesearch_decay, max_linesearch_iter, exit_unconverged, detach_unconverged,
                          backprop, slew_rate_penalty, solver_type, add_goal_constraint, x_goal, diag_cost, ineqG,
                          ineqh, state_estimator, dtype, **kw)
+        if not diag_cost:
+            raise NotImplementedError("Obstacle_MPC: diag_cost=False is not built (the obstacle rows exist in the "
+                                      "nonlinear-caller kernels only, which read diag(C))")
         if n_state < 3:
             raise ValueError("Obstacle_MPC: the obstacle rows act on the position x[0:3] (al_utils.py:316)")
         self.n_obstacles = 40                   # AL_mpc_custom.py:52

@@ -17,6 +17,7 @@
  *   - batch-first row-major layouts, as the reference uses them:
  *       z   [B][T][n]        n = nx+nu, state first        (xu in al_utils.py)
  *       Qd,q[B][T][n]        diagonal of QuadCost.C and QuadCost.c (AL_mpc.py:250)
+ *       C   [B][T][n][n]     all of QuadCost.C, symmetric (alqp_solve_lin_dense_* only)
  *       F   [B][T-1][nx][n]  [A_t B_t]  (dynamics Jacobian, al_utils.py:242-248)
  *       c   [B][T-1][nx]     affine offset of LinDx-style dynamics
  *       xnext[B][T-1][nx]    f(x_t,u_t) evaluated by the caller (nonlinear mode)
@@ -160,6 +161,27 @@ int alqp_solve_lin_f64(const AlqpDims *dims, const AlqpParams *prm, const void *
                        void *phi, void *rnorm2, int *info, unsigned char *status,
                        void *factor_out, const AlqpTrace *trace, void *workspace, size_t ws_bytes,
                        void *stream);
+
+/*
+ * The same solve with a DENSE stage cost 1/2 z_t' C_t z_t + q_t' z_t: C [B][T][n][n] row-major takes the place of Qd.
+ * C_t must be symmetric (the caller symmetrises; the kernel reads whole rows) and H_tt = C_t + penalty terms positive
+ * definite. The reference sketches this case (al_utils.compute_cost's diag_cost=False branch) but cannot run it.
+ * Team kernel only: no workspace; AlqpParams.variant must be 0 or 1 (ALQP_E_BADARG otherwise); ALQP_E_UNSUPPORTED when
+ * the horizon's LDS image does not fit (alqp_supported_variant(dims, is_f64, 1): the image is that of the plain team
+ * kernel, row hi of C_t lives in registers). Every flag of alqp_solve_lin_* except ALQP_WS_PRIMED (ignored), skip_flag
+ * and trace work as there. factor_out is the packed factor alqp_backward_* takes; with w = q_grad of that call the
+ * gradient w.r.t. C is 0.5 (w z_final' + z_final w') per stage, which the caller forms (Qd_grad is its diagonal).
+ */
+int alqp_solve_lin_dense_f32(const AlqpDims *dims, const AlqpParams *prm, const void *C, const void *q,
+                             const void *F, const void *c, const void *x0, const void *u_lo,
+                             const void *u_hi, long sb_u, long st_u, void *z, void *lam, void *rho,
+                             void *phi, void *rnorm2, int *info, unsigned char *status,
+                             void *factor_out, const AlqpTrace *trace, void *stream);
+int alqp_solve_lin_dense_f64(const AlqpDims *dims, const AlqpParams *prm, const void *C, const void *q,
+                             const void *F, const void *c, const void *x0, const void *u_lo,
+                             const void *u_hi, long sb_u, long st_u, void *z, void *lam, void *rho,
+                             void *phi, void *rnorm2, int *info, unsigned char *status,
+                             void *factor_out, const AlqpTrace *trace, void *stream);
 
 /*
  * One Newton direction for the nonlinear-caller mode: the caller evaluated
