@@ -164,6 +164,37 @@ int solve_lin_dense_impl(const AlqpDims *dims, const AlqpParams *prm, const void
     return dispatch_solve_dense<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
 }
 
+// State box rows xlo <= x_t <= xhi: the team kernel only, like the dense cost (the quad kernels know no such rows).
+template <typename real>
+int solve_lin_xbox_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
+                        const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                        const void *x_lo, const void *x_hi, long sb_x, long st_x, void *z, void *lam, void *rho,
+                        void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,
+                        const AlqpTrace *trace, void *stream) {
+    if (!dims_ok(dims) || !prm || !Qd || !q || !F || !c || !x0 || !u_lo || !u_hi || !x_lo || !x_hi || !z || !lam ||
+        !rho || !phi)
+        return ALQP_E_BADARG;
+    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
+    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
+    if (sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
+    // the horizon must fit the team's LDS image (that of the plain kernel): there is no quad kernel to fall back on
+    const size_t lds = lds_query<real>(dims->nx, dims->nu, dims->T);
+    if (lds == 0 || lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    XboxSolveArgs<real> a = {};
+    if (!set_solve<real>(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+        return ALQP_E_BADARG;
+    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
+    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
+    TraceArgs<real> tr = {};
+    if (trace) {
+        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
+        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
+    }
+    return dispatch_solve_xbox<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
+}
+
 // nonlinear fused solve: workspace = [records | F linearisations [B][T-1][nx][n]]
 template <typename real>
 size_t nonlin_ws_bytes(int nx, int nu, int B, int T) {
@@ -261,7 +292,7 @@ int backward_impl(const AlqpDims *dims, const void *factor, void *workspace, siz
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 13; }
+int alqp_abi_version(void) { return 14; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -343,6 +374,17 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
         return alqp::solve_lin_dense_impl<REAL>(dims, prm, C, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, \
                                                 lam, rho, phi, rnorm2, info, status, factor_out,      \
                                                 trace, stream);                                       \
+    }                                                                                                 \
+    int alqp_solve_lin_xbox_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,        \
+                                  const void *q, const void *F, const void *c, const void *x0,        \
+                                  const void *u_lo, const void *u_hi, long sb_u, long st_u,           \
+                                  const void *x_lo, const void *x_hi, long sb_x, long st_x, void *z,  \
+                                  void *lam, void *rho, void *phi, void *rnorm2, int *info,           \
+                                  unsigned char *status, void *factor_out, const AlqpTrace *trace,    \
+                                  void *stream) {                                                     \
+        return alqp::solve_lin_xbox_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u,    \
+                                               x_lo, x_hi, sb_x, st_x, z, lam, rho, phi, rnorm2,      \
+                                               info, status, factor_out, trace, stream);              \
     }                                                                                                 \
     int alqp_newton_step_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
                                const void *x0, const void *lam, const void *rho, const void *Qd,      \

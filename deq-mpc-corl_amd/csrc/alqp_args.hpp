@@ -34,6 +34,13 @@ struct DenseSolveArgs : SolveArgs<real> {
     const real *C;   // [B][T][n][n] row-major, symmetric
 };
 
+// The state-bound fused solve (k_solve_lin_xbox): the state box bounds behind the plain arguments, again in a type of its own.
+template <typename real>
+struct XboxSolveArgs : SolveArgs<real> {
+    const real *xlo, *xhi;   // [nx] (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx)
+    long sb_x, st_x;         // words from one instance's / one stage's bounds to the next
+};
+
 // sum of one value per workgroup over the whole (cooperatively launched) grid, the same bits in every lane of every
 // workgroup: partials in workgroup order, 64 interleaved chains, xor butterfly. Every workgroup must call it.
 __device__ inline double grid_sum_ordered(double block_val, double *scratch, int &phase) {

@@ -1,6 +1,6 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
-#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT)
+#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -28,14 +28,20 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // The dense-cost unit (-DALQP_DENSE_UNIT) compiles this same body as k_solve_lin_dense: the stage cost's full C_t at a.C,
 // [B][T][N][N], in place of a.Qd; uncapped builds only. Two headers over one body, rather than a shared device function:
 // called through one, every plain instantiation came out with different register allocation.
-#ifdef ALQP_DENSE_UNIT
+// The state-bound unit (-DALQP_XBOX_UNIT) is made the same way, a third header: k_solve_lin_xbox, state box rows
+// xlo <= x_t <= xhi behind every stage's control rows (Team's XBOX flag), the bounds at a.xlo / a.xhi; uncapped builds only.
+#if defined(ALQP_DENSE_UNIT)
 template <typename real, int NX, int NU, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_dense(DenseSolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = true;
+    constexpr bool DENSE = true, XBOX = false;
+#elif defined(ALQP_XBOX_UNIT)
+template <typename real, int NX, int NU, bool TRACE>
+__global__ __launch_bounds__(64, 1) void k_solve_lin_xbox(XboxSolveArgs<real> a, TraceArgs<real> tr) {
+    constexpr bool DENSE = false, XBOX = true;
 #else
 template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
 __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = false;
+    constexpr bool DENSE = false, XBOX = false;
 #endif
     if (a.skip && *a.skip != 0.0) return;  // block-uniform, before any barrier
     using C = Cfg<real, NX, NU>;
@@ -46,9 +52,9 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     const int b_raw = blockIdx.x * C::QPW + team;
     const bool active = b_raw < a.B;
     const int b = active ? b_raw : a.B - 1;
-    const int T = a.T, M = C::M(T), neq = T * NX;
+    const int T = a.T, M = C::M(T) + (XBOX ? 2 * T * NX : 0), neq = T * NX;
 
-    Team<real, NX, NU, DENSE> tm;
+    Team<real, NX, NU, DENSE, XBOX> tm;
 #ifdef ALQP_PHASE_TIMING
     for (int i = 0; i < 8; ++i) tm.tacc[i] = 0;
     tm.stamp(-1);
@@ -66,6 +72,11 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.gulo = a.ulo + (size_t)b * a.sb_u;
     tm.guhi = a.uhi + (size_t)b * a.sb_u;
     tm.st_u = a.st_u;
+#ifdef ALQP_XBOX_UNIT
+    tm.gxlo = a.xlo + (size_t)b * a.sb_x;
+    tm.gxhi = a.xhi + (size_t)b * a.sb_x;
+    tm.st_x = a.st_x;
+#endif
 
     real *gz = a.z + (size_t)b * T * N;
     tm.lams = a.lam + (size_t)b * M;  // multipliers stay in global memory (L2), updated in place
@@ -356,7 +367,7 @@ inline long team_simds() {   // SIMDs of the device (4 per CU)
     return n;
 }
 
-#ifndef ALQP_DENSE_UNIT
+#if !defined(ALQP_DENSE_UNIT) && !defined(ALQP_XBOX_UNIT)
 template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
@@ -377,12 +388,20 @@ int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream) {
     });
 }
 
-#else
+#elif defined(ALQP_DENSE_UNIT)
 template <typename real>
 int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
         if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
         return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
+    });
+}
+#else
+template <typename real>
+int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin_xbox<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
+        return launch_team_kernel<real, NX, NU>(k_solve_lin_xbox<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
     });
 }
 #endif
@@ -401,8 +420,11 @@ size_t lds_query(int nx, int nu, int T) {
 
 // The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
-// So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT).
-#if defined(ALQP_DENSE_UNIT)
+// So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT) and the state-bound ones (-DALQP_XBOX_UNIT).
+#if defined(ALQP_XBOX_UNIT)
+template int dispatch_solve_xbox<float>(int, int, const XboxSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
+template int dispatch_solve_xbox<double>(int, int, const XboxSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+#elif defined(ALQP_DENSE_UNIT)
 template int dispatch_solve_dense<float>(int, int, const DenseSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_dense<double>(int, int, const DenseSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 #elif !defined(ALQP_BWD_DYN_UNIT)

@@ -198,11 +198,16 @@ __device__ inline void wave_sync() { asm volatile("" ::: "memory"); }
 // ([T][N][N] row-major, this instance) instead of diag(gQd). H lane hi keeps row hi of C_t in registers, fetched a stage
 // ahead like F; the LDS image is the same. Every DENSE statement sits behind `if constexpr`, so the DENSE = false
 // instantiations compile to the code they had before the flag existed.
-template <typename real, int NX, int NU, bool DENSE = false>
+// XBOX (k_solve_lin_xbox only): state box rows xlo[t] <= x_t <= xhi[t] on every stage, behind the stage's control rows:
+// per stage [u - uhi | -u + ulo | x - xhi | -x + xlo], stage stride 2 NU + 2 NX. A state row is +-e_i' like a control
+// row, so H lanes hi < NX add its penalty terms to g and D next to their equality-row terms, and the three T*NU loops
+// below get a T*NX twin. No LDS of its own. Every XBOX statement sits behind `if constexpr`.
+template <typename real, int NX, int NU, bool DENSE = false, bool XBOX = false>
 struct Team {
     using C = Cfg<real, NX, NU>;
     static constexpr int N = C::N, NP = C::NP, NXP = C::NXP, G = C::G, XT = C::XT;
     static constexpr int RB = C::RB, HP = C::HP;
+    static constexpr int XR = XBOX ? 2 * NX : 0;   // state box rows per stage (behind the 2 NU control rows)
 
     // LDS
     real *Fs, *Ft, *Sb, *Hs, *vs, *gs, *rs;
@@ -225,6 +230,8 @@ struct Team {
     real obs_r2;
     bool no_init;       // state-estimator variant: no initial-state rows, zero cost gradient on u (al_utils_se.py:186-200, 300-310)
     const real *gC;     // DENSE only: this instance's C, [T][N][N] (global memory)
+    const real *gxlo, *gxhi;   // XBOX only: this instance's state bounds, stage stride st_x (global memory)
+    long st_x;
 
 #ifdef ALQP_PHASE_TIMING
     // debug build only (tools/team_timing.py): cycles per phase of the team kernel. Buckets: 0 stage inputs + gradient,
@@ -273,6 +280,7 @@ struct Team {
         gxnext = nullptr;
         gobs = nullptr; nobs = 0; obs_r2 = 0; no_init = false;
         gC = nullptr;
+        gxlo = nullptr; gxhi = nullptr; st_x = 0;
         // constant zero rows / pads of the SYRK operands
         for (int e = li; e < RB * NXP; e += G) Ft[e] = 0;
         for (int e = li; e < RB * NP; e += G) Sb[e] = 0;
@@ -284,6 +292,8 @@ struct Team {
 
     __device__ real uhi(int t, int j) const { return guhi[t * st_u + j]; }
     __device__ real ulo(int t, int j) const { return gulo[t * st_u + j]; }
+    __device__ real xhi(int t, int i) const { return gxhi[t * st_x + i]; }
+    __device__ real xlo(int t, int i) const { return gxlo[t * st_x + i]; }
 
     static constexpr int FCH = (NX * N + G - 1) / G;  // F words per lane
 
@@ -364,12 +374,21 @@ struct Team {
         if (isHx) lan = lams[(T - 1) * NX + hi];
         if (isHu) { lan = lams[T * NX + (hi - NX)]; lbn = lams[T * NX + NU + (hi - NX)]; }
         if (isW) lan = lams[wr];
+        // XBOX, x rows: upper / lower state-bound multipliers and the two bounds, fetched a stage ahead like the rest
+        real lxun = 0, lxln = 0, bxun = 0, bxln = 0;
+        if constexpr (XBOX) {
+            if (isHx) {
+                lxun = lams[T * NX + 2 * NU + hi]; lxln = lams[T * NX + 2 * NU + NX + hi];
+                bxun = xhi(0, hi); bxln = xlo(0, hi);
+            }
+        }
         // Sb may hold s_eq of the previous Newton step: restore its constant zero rows
         for (int e = li; e < RB * NP; e += G) Sb[e] = 0;
         TSTAMP(7);
         for (int t = 0; t < T; ++t) {
             const bool dyn = t < T - 1;
             const real Qv = Qn, qv = qn, cv = cn, la = lan, lb = lbn;
+            const real lxu = lxun, lxl = lxln, bxu = bxun, bxl = bxln;
             if constexpr (DENSE) {
 #pragma unroll
                 for (int k = 0; k < N; ++k) cr[k] = crn[k];
@@ -407,8 +426,15 @@ struct Team {
             if (t + 1 < T) {
                 if (isHx) lan = lams[t * NX + hi];
                 if (isHu) {
-                    lan = lams[T * NX + (t + 1) * (2 * NU + nobs) + (hi - NX)];
-                    lbn = lams[T * NX + (t + 1) * (2 * NU + nobs) + NU + (hi - NX)];
+                    lan = lams[T * NX + (t + 1) * (2 * NU + XR + nobs) + (hi - NX)];
+                    lbn = lams[T * NX + (t + 1) * (2 * NU + XR + nobs) + NU + (hi - NX)];
+                }
+                if constexpr (XBOX) {
+                    if (isHx) {
+                        lxun = lams[T * NX + (t + 1) * (2 * NU + XR) + 2 * NU + hi];
+                        lxln = lams[T * NX + (t + 1) * (2 * NU + XR) + 2 * NU + NX + hi];
+                        bxun = xhi(t + 1, hi); bxln = xlo(t + 1, hi);
+                    }
                 }
             }
             // ---- dynamics residual r_t and multiplier estimate v = lam + rho r (W lanes)
@@ -447,6 +473,13 @@ struct Team {
                     if (!(no_init && t == 0)) {
                         g += fma_(rho, req[row], la);
                         D += rho;
+                    }
+                    if constexpr (XBOX) {
+                        // state box rows of x_t[hi] (stage 0 included): the control rows' terms, with their conventions
+                        real vu = zv - bxu, vl = -zv + bxl;
+                        real au = vu >= 0 ? real(1) : real(0), al = vl >= 0 ? real(1) : real(0);
+                        D = fma_(rho, au + al, D);
+                        g += fma_(rho, vu > 0 ? vu : real(0), lxu) - fma_(rho, vl > 0 ? vl : real(0), lxl);
                     }
                 } else {
                     int j = hi - NX;
@@ -791,7 +824,7 @@ struct Team {
         for (int e = li; e < T * NU; e += G) {
             int t = e / NU, j = e - t * NU;
             real z = zs[t * N + NX + j], d = at_z ? real(0) : ds[t * N + NX + j];
-            int ru = neq + t * 2 * NU + j;
+            int ru = neq + t * (2 * NU + XR) + j;
             real lu = lams[ru], ll = lams[ru + NU];
             real bu = uhi(t, j), bl = ulo(t, j);
             real alpha = 1;
@@ -802,6 +835,24 @@ struct Team {
                 real cu = fmax_(vu, real(0)), cl = fmax_(vl, real(0));
                 acc[k] += fma_(lu, vu, ll * vl) + real(0.5) * rho * fma_(cu, cu, cl * cl);
                 alpha *= real(0.5);
+            }
+        }
+        if constexpr (XBOX) {
+            for (int e = li; e < T * NX; e += G) {
+                int t = e / NX, i = e - t * NX;
+                real z = zs[t * N + i], d = at_z ? real(0) : ds[t * N + i];
+                int ru = neq + t * (2 * NU + XR) + 2 * NU + i;
+                real lu = lams[ru], ll = lams[ru + NX];
+                real bu = xhi(t, i), bl = xlo(t, i);
+                real alpha = 1;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    real zk = fma_(alpha, d, z);
+                    real vu = zk - bu, vl = bl - zk;
+                    real cu = fmax_(vu, real(0)), cl = fmax_(vl, real(0));
+                    acc[k] += fma_(lu, vu, ll * vl) + real(0.5) * rho * fma_(cu, cu, cl * cl);
+                    alpha *= real(0.5);
+                }
             }
         }
         c0 = team_sum<G>(c0);
@@ -826,6 +877,15 @@ struct Team {
             real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
             acc += fma_(cu, cu, cl * cl);
         }
+        if constexpr (XBOX) {
+            for (int e = li; e < T * NX; e += G) {
+                int t = e / NX, i = e - t * NX;
+                real x = zs[t * N + i];
+                real vu = x - xhi(t, i), vl = -x + xlo(t, i);
+                real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+                acc += fma_(cu, cu, cl * cl);
+            }
+        }
         return team_sum<G>(acc);
     }
 
@@ -836,11 +896,22 @@ struct Team {
         for (int e = li; e < T * NU; e += G) {
             int t = e / NU, j = e - t * NU;
             real u = zs[t * N + NX + j];
-            int ru = neq + t * 2 * NU + j, rl = ru + NU;
+            int ru = neq + t * (2 * NU + XR) + j, rl = ru + NU;
             real a = fma_(rho, u - uhi(t, j), lams[ru]);
             real c = fma_(rho, -u + ulo(t, j), lams[rl]);
             lams[ru] = a < 0 ? real(0) : a;
             lams[rl] = c < 0 ? real(0) : c;
+        }
+        if constexpr (XBOX) {
+            for (int e = li; e < T * NX; e += G) {
+                int t = e / NX, i = e - t * NX;
+                real x = zs[t * N + i];
+                int ru = neq + t * (2 * NU + XR) + 2 * NU + i, rl = ru + NX;
+                real a = fma_(rho, x - xhi(t, i), lams[ru]);
+                real c = fma_(rho, -x + xlo(t, i), lams[rl]);
+                lams[ru] = a < 0 ? real(0) : a;
+                lams[rl] = c < 0 ? real(0) : c;
+            }
         }
         wave_sync();
     }

@@ -71,10 +71,11 @@ class _Launcher:
     site states only what differs (al_iter, max_newton, flags, skip, newton_counts, workspace / variant). Also here:
     the backend's capabilities, each probed once with one default, and the scratch the launches share."""
 
-    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once):
+    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once, xbnd=None):
         self.be, self.st, self.dims, self.Qd, self.q, self.F, self.c = be, st, dims, Qd, q, F, c
         self.linearize_once = linearize_once   # F, c are the linearisation frozen at the warm start
         self.dense = Qd.dim() == 4             # Qd is all of C [B,T,n,n] (MPC(diag_cost=False)): solve_lin_dense, team kernel
+        self.xbnd = xbnd                       # (xlo, xhi, sb_x, st_x) of MPC(x_lower=, x_upper=): solve_lin_xbox, team kernel
         self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
         self.has_backward_ws = hasattr(be, "backward_ws")
         self.has_solve_nonlin = hasattr(be, "solve_nonlin")
@@ -99,6 +100,10 @@ class _Launcher:
 
     def lin(self, info=True, **kw):
         st = self.st
+        if self.xbnd is not None:
+            return self.be.solve_lin_xbox(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, *self.xbnd, st.z,
+                                          st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
+                                          **self._out, **kw)
         solve = self.be.solve_lin_dense if self.dense else self.be.solve_lin
         return solve(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, st.z, st.lam, st.rho,
                      self.phi, info=self.info if info else None, n_ls=N_LS, **self._out, **kw)
@@ -112,7 +117,7 @@ class _Launcher:
         dtype, and nothing between this solve's launches (dx / dx_jac included) may make it grow its cache."""
         on = self.private_kw if private else {}
         wsx = on.get("workspace")
-        if wsx is None and self.cached_ws is not None and not self.dense:   # (no quad kernel reads a dense cost)
+        if wsx is None and self.cached_ws is not None and not self.dense and self.xbnd is None:   # (no quad kernel reads a dense cost or state-bound rows)
             if self._cached is None:
                 self._cached = self.cached_ws(self.dims, self.st.z)[0]
             wsx = self._cached
@@ -161,6 +166,10 @@ class _ALSolve(torch.autograd.Function):
     Dense cost (``MPC(diag_cost=False)``): ``Qd`` is all of C, [B,T,n,n] and symmetric, and its gradient is
     0.5 (w z_final' + z_final w') per stage, formed here from the unchanged backward call's w = q_grad (its diagonal is
     the Qd_grad of the diagonal case).
+
+    State bounds (``MPC(x_lower=, x_upper=)``): nothing changes here. The saved factor is that of the last Newton step's
+    H, whose diagonal holds rho for every state-bound row active there, so w is taken with the active set held fixed,
+    the approximation the control-bound rows already make.
     """
 
     @staticmethod
@@ -222,6 +231,7 @@ class MPC(Module):
 
         min_{x,u} sum_t 1/2 tau_t' C_t tau_t + c_t' tau_t     tau_t = [x_t; u_t]
         s.t.      x_{t+1} = f(x_t, u_t),  x_0 = x_init,  u_lower <= u <= u_upper
+                  x_lower <= x_t <= x_upper  for all T stages (optional; stage 0 included)
 
     Differentiable w.r.t. the cost (diag C and c, as the reference). ``diag_cost=False``: C_t is a full matrix (cross
     terms, a Riccati terminal cost, a rotated frame); its symmetric part enters the solve and the gradient reaches all of
@@ -230,6 +240,14 @@ class MPC(Module):
     [B,T-1,nx,n], f [B,T-1,nx], no broadcast over the batch) the solve is also differentiable w.r.t. ``F``, ``f`` and
     ``x0`` (see ``_ALSolve``); not on the streaming route (``NotImplementedError``). With a callable ``dx`` there are
     no such gradients: ``x0.grad`` stays ``None``.
+
+    ``x_lower`` / ``x_upper`` (both or neither): box constraints on the states, each a number, [nx], or
+    anything that broadcasts to [B,T,nx] (per-stage bounds can relax stage 0, whose state is pinned to x0). A non-finite
+    entry means "no bound". The reference carries the two arguments but never built their rows (al_utils.py:294-302
+    are commented out). ``lamda_prev`` is then [B, T nx + T (2 nu + 2 nx)]: the equality rows, then per stage
+    [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower]. LinDx routes only (the fused team kernel, at any
+    batch): not with a callable ``dx``, ``linearize_once``, ``state_estimator``, ``Obstacle_MPC`` or ``diag_cost=False``.
+    All gradients above stay available, taken with the active set held fixed.
     """
 
     def __init__(self, n_state, n_ctrl, T, u_lower=None, u_upper=None, u_init=None, x_init=None,
@@ -239,7 +257,7 @@ class MPC(Module):
                  solver_type="dense", add_goal_constraint=False, x_goal=None, diag_cost=True,
                  ineqG=None, ineqh=None, state_estimator=False, dtype=torch.float64,
                  exit_mode="reference", backend=None, process_group=None, prefer_fused=False,
-                 check_numerics=None, exit_in_kernel="auto"):
+                 check_numerics=None, exit_in_kernel="auto", x_lower=None, x_upper=None):
         super().__init__()
         if (u_lower is None) != (u_upper is None) or u_lower is None:
             raise ValueError("MPC: u_lower and u_upper are both required (AL_mpc.py:145,152)")
@@ -251,10 +269,28 @@ class MPC(Module):
                                       "nonlinear-caller kernels, which read diag(C)")
         if exit_mode not in ("reference", "fixed"):
             raise ValueError("exit_mode must be 'reference' or 'fixed'")
+        if (x_lower is None) != (x_upper is None):
+            raise ValueError("MPC: x_lower and x_upper go together (pass +-inf for a side without a bound)")
+        if x_lower is not None:
+            # the state-bound rows live in the fused team kernel of the LinDx routes alone (alqp_solve_lin_xbox)
+            if state_estimator:
+                raise NotImplementedError("MPC: x_lower / x_upper with state_estimator: that variant runs on the "
+                                          "nonlinear-caller kernels, which know no state-bound rows")
+            if not diag_cost:
+                raise NotImplementedError("MPC: x_lower / x_upper with diag_cost=False: no kernel instance takes "
+                                          "both the dense cost and the state-bound rows")
         self.dtype = dtype
         self.n_state, self.n_ctrl, self.T = n_state, n_ctrl, T
         self.u_lower = _detach_maybe(torch.as_tensor(u_lower).to(dtype))
         self.u_upper = _detach_maybe(torch.as_tensor(u_upper).to(dtype))
+        self.x_lower = self.x_upper = None
+        if x_lower is not None:
+            # a non-finite entry is "no bound": a bound no state reaches, inert for every rho <= rho_max like the state
+            # estimator's control rows (a literal infinity would make lam * r NaN in the merit)
+            self.x_lower = torch.nan_to_num(_detach_maybe(torch.as_tensor(x_lower).to(dtype)), nan=-SE_NO_BOUND,
+                                            posinf=SE_NO_BOUND, neginf=-SE_NO_BOUND)
+            self.x_upper = torch.nan_to_num(_detach_maybe(torch.as_tensor(x_upper).to(dtype)), nan=SE_NO_BOUND,
+                                            posinf=SE_NO_BOUND, neginf=-SE_NO_BOUND)
         self.u_init = _detach_maybe(u_init)
         self.x_init = _detach_maybe(x_init)
         self.al_iter = al_iter
@@ -268,6 +304,8 @@ class MPC(Module):
         self.state_estimator = bool(state_estimator)
         self.neq = n_state * (T - 1) if self.state_estimator else n_state * T
         self.nineq = 0 if self.state_estimator else 2 * n_ctrl * T
+        if self.x_lower is not None:
+            self.nineq += 2 * n_state * T   # AL_mpc.py:198-201
         self.rho_prev = 1.0
         self.rho_max = 1e8
         self.dyn_res_prev = 1000000
@@ -485,6 +523,17 @@ class MPC(Module):
         lo = lo.expand(B, self.T, nu).contiguous()
         hi = hi.expand(B, self.T, nu).contiguous()
         return lo, hi, self.T * nu, nu
+
+    def _xbounds(self, B, dtype, device):
+        """(xlo, xhi, sb_x, st_x) as alqp_solve_lin_xbox takes them, or None without state bounds."""
+        if self.x_lower is None:
+            return None
+        nx = self.n_state
+        lo = self.x_lower.to(device=device, dtype=dtype)
+        hi = self.x_upper.to(device=device, dtype=dtype)
+        if lo.dim() <= 1 and hi.dim() <= 1:
+            return lo.reshape(-1).expand(nx).contiguous(), hi.reshape(-1).expand(nx).contiguous(), 0, 0
+        return lo.expand(B, self.T, nx).contiguous(), hi.expand(B, self.T, nx).contiguous(), self.T * nx, nx
 
     def _rho_tensor(self, B, dtype, device):
         r = self.rho_prev
@@ -795,6 +844,21 @@ class MPC(Module):
             if st.lin is None:
                 raise NotImplementedError("MPC: diag_cost=False needs affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models read diag(C)")
+        if self.x_lower is not None:
+            # the state-bound rows live in the fused team kernel alone (alqp_solve_lin_xbox): the launch-per-step helper
+            # kernels, k_newton_step* and the compiled-in models know no such rows
+            if self._has_extra_rows():
+                raise NotImplementedError("MPC: x_lower / x_upper with obstacle rows (Obstacle_MPC): those run on the "
+                                          "nonlinear-caller kernels, which know no state-bound rows")
+            if self.linearize_once:
+                raise NotImplementedError("MPC: x_lower / x_upper with linearize_once: the frozen-linearisation route "
+                                          "evaluates merit and dual update with kernels that know no state-bound rows")
+            if st.lin is None:
+                raise NotImplementedError("MPC: x_lower / x_upper need affine dynamics given as LinDx(F, f): the "
+                                          "nonlinear-caller kernels and the compiled-in models know no state-bound rows")
+            if st.lam.shape[1] != self.neq + self.nineq:
+                raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the state bounds need "
+                                 f"{self.neq + self.nineq} = T nx + T (2 nu + 2 nx)")
         if self.state_estimator:
             # cost gradient on the states only (al_utils_se.py:300-310) while the Hessian keeps diag(Q) on the
             # controls (:66-68): the kernels' `state_estimator` flag. Their merit still counts the controls' cost
@@ -827,9 +891,10 @@ class MPC(Module):
         elif st.lin is not None:
             F = st.lin[0].detach().to(device=dev, dtype=dt).contiguous()
             c = st.lin[1].detach().to(device=dev, dtype=dt).contiguous()
-        L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once)
+        L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once, self._xbounds(B, dt, dev))
         # the quad kernels take the obstacle / state-estimator rows too, so their factor can stay in the records
-        use_qws = need_grad and L.has_backward_ws and B >= L.quad_min_batch and not L.dense   # dense: packed factor
+        # (dense cost, state bounds: team kernel, packed factor)
+        use_qws = need_grad and L.has_backward_ws and B >= L.quad_min_batch and not L.dense and L.xbnd is None
         if use_qws:
             L.qws = be.new_workspace(dims, st.z)
             L.private_kw = dict(workspace=L.qws, variant="quad")

@@ -184,6 +184,33 @@ int alqp_solve_lin_dense_f64(const AlqpDims *dims, const AlqpParams *prm, const 
                              void *factor_out, const AlqpTrace *trace, void *stream);
 
 /*
+ * The same solve with STATE BOX ROWS x_lo[t] <= x_t <= x_hi[t] on all T stages (stage 0 included) next to the control
+ * bounds. x_lo / x_hi: [nx] shared by every instance and stage (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx).
+ * Entries must be finite: "no bound" is a bound no state reaches whose product with the largest rho stays finite (the
+ * host uses +-1e20); an infinity would make lam * r NaN in the merit. The reference carries x_lower / x_upper
+ * (AL_mpc.py:154-155) but leaves their rows commented out (al_utils.py:294-302) and cannot run this case.
+ * lam is [B][M] with M = T nx + T (2 nu + 2 nx): the T nx equality rows as everywhere, then per stage
+ * [u - u_hi | -u + u_lo | x - x_hi | -x + x_lo] (the order of al_utils.py:293-302). Conventions of the control rows:
+ * Hessian term where the residual is >= 0, gradient and merit terms max(r, 0), dual update max(0, lam + rho r).
+ * Team kernel only: no workspace; AlqpParams.variant must be 0 or 1 (ALQP_E_BADARG otherwise); ALQP_E_UNSUPPORTED when
+ * the horizon's LDS image does not fit (that of the plain team kernel: the rows need no LDS). Flags, skip_flag and trace
+ * as alqp_solve_lin_dense_*. factor_out is the packed factor alqp_backward_* takes unchanged (the active rows' penalty
+ * terms are on its diagonal: the active set is held fixed in the backward pass).
+ */
+int alqp_solve_lin_xbox_f32(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                            const void *F, const void *c, const void *x0, const void *u_lo,
+                            const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                            long sb_x, long st_x, void *z, void *lam, void *rho, void *phi, void *rnorm2,
+                            int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
+                            void *stream);
+int alqp_solve_lin_xbox_f64(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                            const void *F, const void *c, const void *x0, const void *u_lo,
+                            const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                            long sb_x, long st_x, void *z, void *lam, void *rho, void *phi, void *rnorm2,
+                            int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
+                            void *stream);
+
+/*
  * One Newton direction for the nonlinear-caller mode: the caller evaluated
  * dx_jac(x,u) -> (xnext, F) in PyTorch (al_utils.py:233-248). Replaces
  * merit_grad_hessian (:80-123) + cholesky_ex/cholesky_solve (:510-515).
