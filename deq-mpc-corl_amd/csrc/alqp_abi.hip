@@ -195,6 +195,41 @@ int solve_lin_xbox_impl(const AlqpDims *dims, const AlqpParams *prm, const void 
     return dispatch_solve_xbox<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
 }
 
+// General rows G_t z_t <= h_t: the team kernel only (the quad kernels know no such rows), no workspace.
+template <typename real>
+int solve_lin_poly_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
+                        const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                        const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h, void *z,
+                        void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
+                        void *factor_out, const AlqpTrace *trace, void *stream) {
+    if (!dims_ok(dims) || !prm || !Qd || !q || !F || !c || !x0 || !u_lo || !u_hi || !G || !h || !z || !lam || !rho ||
+        !phi)
+        return ALQP_E_BADARG;
+    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
+    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
+    if (m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
+    // the horizon must fit the LDS: the team image plus the hand-over region of 2 pad4(m) words per team (there is no
+    // quad kernel to fall back on)
+    const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
+    if (img == 0) return ALQP_E_UNSUPPORTED;
+    const size_t lds = img + (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real);
+    if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    PolySolveArgs<real> a = {};
+    if (!set_solve<real>(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+        return ALQP_E_BADARG;
+    a.G = (const real *)G; a.h = (const real *)h; a.m = m;
+    a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
+    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
+    TraceArgs<real> tr = {};
+    if (trace) {
+        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
+        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
+    }
+    return dispatch_solve_poly<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
+}
+
 // nonlinear fused solve: workspace = [records | F linearisations [B][T-1][nx][n]]
 template <typename real>
 size_t nonlin_ws_bytes(int nx, int nu, int B, int T) {
@@ -292,7 +327,7 @@ int backward_impl(const AlqpDims *dims, const void *factor, void *workspace, siz
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 14; }
+int alqp_abi_version(void) { return 15; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -385,6 +420,17 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
         return alqp::solve_lin_xbox_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u,    \
                                                x_lo, x_hi, sb_x, st_x, z, lam, rho, phi, rnorm2,      \
                                                info, status, factor_out, trace, stream);              \
+    }                                                                                                 \
+    int alqp_solve_lin_poly_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,        \
+                                  const void *q, const void *F, const void *c, const void *x0,        \
+                                  const void *u_lo, const void *u_hi, long sb_u, long st_u,           \
+                                  const void *G, const void *h, int m, long sb_g, long st_g,          \
+                                  long sb_h, long st_h, void *z, void *lam, void *rho, void *phi,     \
+                                  void *rnorm2, int *info, unsigned char *status, void *factor_out,   \
+                                  const AlqpTrace *trace, void *stream) {                             \
+        return alqp::solve_lin_poly_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u,    \
+                                               G, h, m, sb_g, st_g, sb_h, st_h, z, lam, rho, phi,     \
+                                               rnorm2, info, status, factor_out, trace, stream);      \
     }                                                                                                 \
     int alqp_newton_step_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
                                const void *x0, const void *lam, const void *rho, const void *Qd,      \

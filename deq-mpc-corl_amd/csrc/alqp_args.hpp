@@ -41,6 +41,16 @@ struct XboxSolveArgs : SolveArgs<real> {
     long sb_x, st_x;         // words from one instance's / one stage's bounds to the next
 };
 
+// The fused solve with stage-wise linear rows G_t z_t <= h_t (k_solve_lin_poly): the rows behind the plain arguments, again
+// in a type of its own.
+template <typename real>
+struct PolySolveArgs : SolveArgs<real> {
+    const real *G, *h;   // G: [m][n] (sb_g = st_g = 0), [T][m][n] (0, m n) or [B][T][m][n] (T m n, m n); h likewise without [n]
+    int m;               // rows per stage, 1 .. 64
+    long sb_g, st_g;     // words from one instance's / one stage's G to the next
+    long sb_h, st_h;
+};
+
 // sum of one value per workgroup over the whole (cooperatively launched) grid, the same bits in every lane of every
 // workgroup: partials in workgroup order, 64 interleaved chains, xor butterfly. Every workgroup must call it.
 __device__ inline double grid_sum_ordered(double block_val, double *scratch, int &phase) {

@@ -22,6 +22,8 @@ template <typename real>
 inline int flags_of(const DenseSolveArgs<real> &a) { return a.flags; }
 template <typename real>
 inline int flags_of(const XboxSolveArgs<real> &a) { return a.flags; }
+template <typename real>
+inline int flags_of(const PolySolveArgs<real> &a) { return a.flags; }
 template <typename Fn, typename A0, typename... Rest>
 int launch_maybe_coop(Fn fn, unsigned grid, size_t lds, hipStream_t stream, A0 a0, Rest... rest) {
     if (flags_of(a0) & ALQP_EXIT_IN_KERNEL) {
@@ -67,6 +69,8 @@ template <typename real>
 int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
+template <typename real>
+int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 size_t lds_query(int nx, int nu, int T);   // bytes of the team LDS image, 0: no such instance
 

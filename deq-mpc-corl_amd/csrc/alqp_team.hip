@@ -1,6 +1,6 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
-#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT)
+#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT) || defined(ALQP_POLY_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -30,18 +30,26 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // called through one, every plain instantiation came out with different register allocation.
 // The state-bound unit (-DALQP_XBOX_UNIT) is made the same way, a third header: k_solve_lin_xbox, state box rows
 // xlo <= x_t <= xhi behind every stage's control rows (Team's XBOX flag), the bounds at a.xlo / a.xhi; uncapped builds only.
+// The general-row unit (-DALQP_POLY_UNIT), a fourth header: k_solve_lin_poly, a.m rows G_t z_t <= h_t behind every stage's
+// control rows (Team's POLY flag), rows and right-hand sides at a.G / a.h. Its LDS image is the team image plus a hand-over
+// region of 2 pad4(a.m) words per team. Uncapped builds only, for the reason given above: a capped build spills, and a
+// spilling build of this body is what the TRACE paragraph describes.
 #if defined(ALQP_DENSE_UNIT)
 template <typename real, int NX, int NU, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_dense(DenseSolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = true, XBOX = false;
+    constexpr bool DENSE = true, XBOX = false, POLY = false;
 #elif defined(ALQP_XBOX_UNIT)
 template <typename real, int NX, int NU, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_xbox(XboxSolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = false, XBOX = true;
+    constexpr bool DENSE = false, XBOX = true, POLY = false;
+#elif defined(ALQP_POLY_UNIT)
+template <typename real, int NX, int NU, bool TRACE>
+__global__ __launch_bounds__(64, 1) void k_solve_lin_poly(PolySolveArgs<real> a, TraceArgs<real> tr) {
+    constexpr bool DENSE = false, XBOX = false, POLY = true;
 #else
 template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
 __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = false, XBOX = false;
+    constexpr bool DENSE = false, XBOX = false, POLY = false;
 #endif
     if (a.skip && *a.skip != 0.0) return;  // block-uniform, before any barrier
     using C = Cfg<real, NX, NU>;
@@ -52,14 +60,20 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     const int b_raw = blockIdx.x * C::QPW + team;
     const bool active = b_raw < a.B;
     const int b = active ? b_raw : a.B - 1;
+#ifdef ALQP_POLY_UNIT
+    const int T = a.T, M = C::M(T) + T * a.m, neq = T * NX;
+    const int team_words = C::team_words(T) + 2 * pad4(a.m);   // the team image, then the hand-over region
+#else
     const int T = a.T, M = C::M(T) + (XBOX ? 2 * T * NX : 0), neq = T * NX;
+    const int team_words = C::team_words(T);
+#endif
 
-    Team<real, NX, NU, DENSE, XBOX> tm;
+    Team<real, NX, NU, DENSE, XBOX, POLY> tm;
 #ifdef ALQP_PHASE_TIMING
     for (int i = 0; i < 8; ++i) tm.tacc[i] = 0;
     tm.stamp(-1);
 #endif
-    tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
+    tm.init(smem + (size_t)team * team_words + opaque_zero(), li, team * G, T, b);
 #ifdef ALQP_DENSE_UNIT
     tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
 #else
@@ -76,6 +90,12 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.gxlo = a.xlo + (size_t)b * a.sb_x;
     tm.gxhi = a.xhi + (size_t)b * a.sb_x;
     tm.st_x = a.st_x;
+#endif
+#ifdef ALQP_POLY_UNIT
+    tm.gG = a.G + (size_t)b * a.sb_g;
+    tm.gh = a.h + (size_t)b * a.sb_h;
+    tm.st_g = a.st_g; tm.st_h = a.st_h; tm.pm = a.m;
+    tm.ps = tm.Xp + pad4(T * C::XT);
 #endif
 
     real *gz = a.z + (size_t)b * T * N;
@@ -341,10 +361,11 @@ size_t lds_bytes_for(int T) {
 }
 
 // Launches `fn` with one wavefront per workgroup and the team LDS image as dynamic LDS.
+// `extra_words`: LDS words per team behind the team image (k_solve_lin_poly's hand-over region).
 template <typename real, int NX, int NU, typename Fn, typename... Args>
-int launch_team_kernel(Fn fn, int B, int T, hipStream_t stream, Args... args) {
+int launch_team_kernel_extra(Fn fn, int B, int T, int extra_words, hipStream_t stream, Args... args) {
     using C = Cfg<real, NX, NU>;
-    const size_t lds = lds_bytes_for<real, NX, NU>(T);
+    const size_t lds = lds_bytes_for<real, NX, NU>(T) + (size_t)C::QPW * extra_words * sizeof(real);
     if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
     const unsigned grid = (unsigned)((B + C::QPW - 1) / C::QPW);
     if (lds > 48 * 1024) {
@@ -353,6 +374,10 @@ int launch_team_kernel(Fn fn, int B, int T, hipStream_t stream, Args... args) {
             return ALQP_E_LAUNCH;
     }
     return launch_maybe_coop(fn, grid, lds, stream, args...);
+}
+template <typename real, int NX, int NU, typename Fn, typename... Args>
+int launch_team_kernel(Fn fn, int B, int T, hipStream_t stream, Args... args) {
+    return launch_team_kernel_extra<real, NX, NU>(fn, B, T, 0, stream, args...);
 }
 
 inline long team_simds() {   // SIMDs of the device (4 per CU)
@@ -367,7 +392,7 @@ inline long team_simds() {   // SIMDs of the device (4 per CU)
     return n;
 }
 
-#if !defined(ALQP_DENSE_UNIT) && !defined(ALQP_XBOX_UNIT)
+#if !defined(ALQP_DENSE_UNIT) && !defined(ALQP_XBOX_UNIT) && !defined(ALQP_POLY_UNIT)
 template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
@@ -396,6 +421,15 @@ int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const Tr
         return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
     });
 }
+#elif defined(ALQP_POLY_UNIT)
+template <typename real>
+int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
+    const int extra = 2 * pad4(a.m);
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (tr) return launch_team_kernel_extra<real, NX, NU>(k_solve_lin_poly<real, NX, NU, true>, a.B, a.T, extra, stream, a, *tr);
+        return launch_team_kernel_extra<real, NX, NU>(k_solve_lin_poly<real, NX, NU, false>, a.B, a.T, extra, stream, a, TraceArgs<real>{});
+    });
+}
 #else
 template <typename real>
 int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
@@ -420,8 +454,12 @@ size_t lds_query(int nx, int nu, int T) {
 
 // The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
-// So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT) and the state-bound ones (-DALQP_XBOX_UNIT).
-#if defined(ALQP_XBOX_UNIT)
+// So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT), the state-bound ones (-DALQP_XBOX_UNIT) and
+// the general-row ones (-DALQP_POLY_UNIT).
+#if defined(ALQP_POLY_UNIT)
+template int dispatch_solve_poly<float>(int, int, const PolySolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
+template int dispatch_solve_poly<double>(int, int, const PolySolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+#elif defined(ALQP_XBOX_UNIT)
 template int dispatch_solve_xbox<float>(int, int, const XboxSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_xbox<double>(int, int, const XboxSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 #elif defined(ALQP_DENSE_UNIT)

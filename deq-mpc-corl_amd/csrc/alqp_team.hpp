@@ -202,7 +202,16 @@ __device__ inline void wave_sync() { asm volatile("" ::: "memory"); }
 // per stage [u - uhi | -u + ulo | x - xhi | -x + xlo], stage stride 2 NU + 2 NX. A state row is +-e_i' like a control
 // row, so H lanes hi < NX add its penalty terms to g and D next to their equality-row terms, and the three T*NU loops
 // below get a T*NX twin. No LDS of its own. Every XBOX statement sits behind `if constexpr`.
-template <typename real, int NX, int NU, bool DENSE = false, bool XBOX = false>
+// POLY (k_solve_lin_poly only): pm >= 1 general rows G_t z_t <= h_t per stage, z_t = [x_t; u_t], behind the stage's control
+// rows: per stage [u - uhi | -u + ulo | G_t z_t - h_t], stage stride 2 NU + pm (pm is a run-time number). Row k of stage t,
+// r = G_k z_t - h_k, adds G_k' (lam_k + rho max(r, 0)) to g_t and rho [r >= 0] G_k' G_k to ALL of H_tt. Per stage the team
+// computes the pm residuals once (lane li takes rows li, li + G, ...; the first trip's row, h and multiplier are fetched a
+// stage ahead like the other stage inputs) and hands weight and activity to the H lanes through `ps`, the kernel's own
+// LDS region of 2 pad4(pm) words per team behind the team image (not part of Cfg::team_words). H lane hi accumulates
+// row hi of the rank-one sum in registers, like DENSE's cr[N], and adds it to row hi of Hs behind the SYRK phase. The
+// three T*NU loops below get a T*pm twin: a row's residual along the Newton direction is r0 + alpha s, two dot products
+// per row and Newton step. Every POLY statement sits behind `if constexpr`.
+template <typename real, int NX, int NU, bool DENSE = false, bool XBOX = false, bool POLY = false>
 struct Team {
     using C = Cfg<real, NX, NU>;
     static constexpr int N = C::N, NP = C::NP, NXP = C::NXP, G = C::G, XT = C::XT;
@@ -232,6 +241,10 @@ struct Team {
     const real *gC;     // DENSE only: this instance's C, [T][N][N] (global memory)
     const real *gxlo, *gxhi;   // XBOX only: this instance's state bounds, stage stride st_x (global memory)
     long st_x;
+    const real *gG, *gh;       // POLY only: this instance's rows [pm][N] and right-hand sides [pm], stage strides st_g / st_h
+    long st_g, st_h;
+    int pm;                    // POLY only: rows per stage
+    real *ps;                  // POLY only, LDS: [pad4(pm)] weights lam_k + rho max(r_k, 0), then [pad4(pm)] rho [r_k >= 0]
 
 #ifdef ALQP_PHASE_TIMING
     // debug build only (tools/team_timing.py): cycles per phase of the team kernel. Buckets: 0 stage inputs + gradient,
@@ -281,6 +294,7 @@ struct Team {
         gobs = nullptr; nobs = 0; obs_r2 = 0; no_init = false;
         gC = nullptr;
         gxlo = nullptr; gxhi = nullptr; st_x = 0;
+        gG = nullptr; gh = nullptr; st_g = 0; st_h = 0; pm = 0; ps = nullptr;
         // constant zero rows / pads of the SYRK operands
         for (int e = li; e < RB * NXP; e += G) Ft[e] = 0;
         for (int e = li; e < RB * NP; e += G) Sb[e] = 0;
@@ -294,6 +308,22 @@ struct Team {
     __device__ real ulo(int t, int j) const { return gulo[t * st_u + j]; }
     __device__ real xhi(int t, int i) const { return gxhi[t * st_x + i]; }
     __device__ real xlo(int t, int i) const { return gxlo[t * st_x + i]; }
+    // POLY: row k of stage t and its right-hand side. (The stage stride of the multipliers is written (POLY ? pm : 0) in
+    // place: through a member function, every instantiation without the flag came out with different register allocation.)
+    __device__ const real *grow(int t, int k) const { return gG + t * st_g + k * N; }
+    __device__ real hrow(int t, int k) const { return gh[t * st_h + k]; }
+    // POLY: residual of one row at stage t's iterate -> weight and activity for the H lanes
+    __device__ void poly_hand_over(int t, int k, const real (&gr)[N], real hv, real lk) {
+        real zr[N];   // operands first, products after (see backward_sweep)
+#pragma unroll
+        for (int j = 0; j < N; ++j) zr[j] = zs[t * N + j];
+        __builtin_amdgcn_sched_barrier(0);
+        real r = -hv;
+#pragma unroll
+        for (int j = 0; j < N; ++j) r = fma_(gr[j], zr[j], r);
+        ps[k] = fma_(rho, r > 0 ? r : real(0), lk);
+        ps[pad4(pm) + k] = r >= 0 ? rho : real(0);
+    }
 
     static constexpr int FCH = (NX * N + G - 1) / G;  // F words per lane
 
@@ -382,6 +412,17 @@ struct Team {
                 bxun = xhi(0, hi); bxln = xlo(0, hi);
             }
         }
+        // POLY: row li of G_0, its right-hand side and multiplier (the first trip of the residual loop), a stage ahead too
+        real grn[POLY ? N : 1], hpn = 0, lpn = 0;
+        real crow[POLY ? N : 1];   // POLY: row hi of rho sum_k [r_k >= 0] G_k' G_k of the stage in hand
+        if constexpr (POLY) {
+            const int k = li < pm ? li : 0;
+            const real *Gk = grow(0, k);
+#pragma unroll
+            for (int j = 0; j < N; ++j) grn[j] = Gk[j];
+            hpn = hrow(0, k);
+            lpn = lams[T * NX + 2 * NU + k];
+        }
         // Sb may hold s_eq of the previous Newton step: restore its constant zero rows
         for (int e = li; e < RB * NP; e += G) Sb[e] = 0;
         TSTAMP(7);
@@ -426,13 +467,13 @@ struct Team {
             if (t + 1 < T) {
                 if (isHx) lan = lams[t * NX + hi];
                 if (isHu) {
-                    lan = lams[T * NX + (t + 1) * (2 * NU + XR + nobs) + (hi - NX)];
-                    lbn = lams[T * NX + (t + 1) * (2 * NU + XR + nobs) + NU + (hi - NX)];
+                    lan = lams[T * NX + (t + 1) * (2 * NU + XR + nobs + (POLY ? pm : 0)) + (hi - NX)];
+                    lbn = lams[T * NX + (t + 1) * (2 * NU + XR + nobs + (POLY ? pm : 0)) + NU + (hi - NX)];
                 }
                 if constexpr (XBOX) {
                     if (isHx) {
-                        lxun = lams[T * NX + (t + 1) * (2 * NU + XR) + 2 * NU + hi];
-                        lxln = lams[T * NX + (t + 1) * (2 * NU + XR) + 2 * NU + NX + hi];
+                        lxun = lams[T * NX + (t + 1) * (2 * NU + XR + (POLY ? pm : 0)) + 2 * NU + hi];
+                        lxln = lams[T * NX + (t + 1) * (2 * NU + XR + (POLY ? pm : 0)) + 2 * NU + NX + hi];
                         bxun = xhi(t + 1, hi); bxln = xlo(t + 1, hi);
                     }
                 }
@@ -449,6 +490,26 @@ struct Team {
                 vs[wr] = fma_(rho, r, la);
             }
             wave_sync();
+            if constexpr (POLY) {
+                // ---- the stage's pm row residuals, once per team: weight and activity into ps for the H lanes
+                if (li < pm) poly_hand_over(t, li, grn, hpn, lpn);
+                for (int k = li + G; k < pm; k += G) {   // pm above the team width: further trips, fetched in place
+                    const real *Gk = grow(t, k);
+                    real gr[N];
+#pragma unroll
+                    for (int j = 0; j < N; ++j) gr[j] = Gk[j];
+                    poly_hand_over(t, k, gr, hrow(t, k), lams[T * NX + t * (2 * NU + pm) + 2 * NU + k]);
+                }
+                if (t + 1 < T) {   // the next stage's first trip: in flight during this stage
+                    const int k = li < pm ? li : 0;
+                    const real *Gk = grow(t + 1, k);
+#pragma unroll
+                    for (int j = 0; j < N; ++j) grn[j] = Gk[j];
+                    hpn = hrow(t + 1, k);
+                    lpn = lams[T * NX + (t + 1) * (2 * NU + pm) + 2 * NU + k];
+                }
+                wave_sync();
+            }
             // ---- gradient entry and diagonal of H_tt (H lanes), al_utils.py:113-120
             real D = 0;
             real hob[3] = {0, 0, 0};   // obstacle rows: rho J_k'J_k entries (hi, 0..2) of the active rows
@@ -519,6 +580,24 @@ struct Team {
                         }
                     }
                 }
+                if constexpr (POLY) {
+                    // g_t[hi] += sum_k w_k G_k[hi]; crow = row hi of sum_k a_k G_k' G_k (w_k, a_k from ps; G_t from L2,
+                    // every H lane of the team reads the same row)
+                    const int mp = pad4(pm);
+#pragma unroll
+                    for (int j = 0; j < N; ++j) crow[j] = 0;
+                    for (int k = 0; k < pm; ++k) {
+                        const real *Gk = grow(t, k);
+                        real gk[N];
+#pragma unroll
+                        for (int j = 0; j < N; ++j) gk[j] = Gk[j];
+                        const real gh_ = Gk[hi];
+                        g = fma_(ps[k], gh_, g);
+                        const real ca = ps[mp + k] * gh_;
+#pragma unroll
+                        for (int j = 0; j < N; ++j) crow[j] = fma_(ca, gk[j], crow[j]);
+                    }
+                }
                 gs[hi] = g;
                 if (g_out) g_out[t * N + hi] = g;
             }
@@ -570,6 +649,18 @@ struct Team {
                         ld4(Hs + hi * HP + k4, h4);
                         st4(Hs + hi * HP + k4, h4[0] + cr[k4], k4 + 1 < N ? h4[1] + cr[k4 + 1] : h4[1],
                             k4 + 2 < N ? h4[2] + cr[k4 + 2] : h4[2], k4 + 3 < N ? h4[3] + cr[k4 + 3] : h4[3]);
+                    }
+                }
+            }
+            if constexpr (POLY) {
+                // row hi of the active rows' rho G_k' G_k on top of row hi of H_tt (symmetric; the panel reads the lower triangle)
+                if (isH) {
+#pragma unroll
+                    for (int k4 = 0; k4 < NP; k4 += 4) {
+                        real h4[4];
+                        ld4(Hs + hi * HP + k4, h4);
+                        st4(Hs + hi * HP + k4, h4[0] + crow[k4], k4 + 1 < N ? h4[1] + crow[k4 + 1] : h4[1],
+                            k4 + 2 < N ? h4[2] + crow[k4 + 2] : h4[2], k4 + 3 < N ? h4[3] + crow[k4 + 3] : h4[3]);
                     }
                 }
             }
@@ -824,7 +915,7 @@ struct Team {
         for (int e = li; e < T * NU; e += G) {
             int t = e / NU, j = e - t * NU;
             real z = zs[t * N + NX + j], d = at_z ? real(0) : ds[t * N + NX + j];
-            int ru = neq + t * (2 * NU + XR) + j;
+            int ru = neq + t * (2 * NU + XR + (POLY ? pm : 0)) + j;
             real lu = lams[ru], ll = lams[ru + NU];
             real bu = uhi(t, j), bl = ulo(t, j);
             real alpha = 1;
@@ -841,7 +932,7 @@ struct Team {
             for (int e = li; e < T * NX; e += G) {
                 int t = e / NX, i = e - t * NX;
                 real z = zs[t * N + i], d = at_z ? real(0) : ds[t * N + i];
-                int ru = neq + t * (2 * NU + XR) + 2 * NU + i;
+                int ru = neq + t * (2 * NU + XR + (POLY ? pm : 0)) + 2 * NU + i;
                 real lu = lams[ru], ll = lams[ru + NX];
                 real bu = xhi(t, i), bl = xlo(t, i);
                 real alpha = 1;
@@ -851,6 +942,28 @@ struct Team {
                     real vu = zk - bu, vl = bl - zk;
                     real cu = fmax_(vu, real(0)), cl = fmax_(vl, real(0));
                     acc[k] += fma_(lu, vu, ll * vl) + real(0.5) * rho * fma_(cu, cu, cl * cl);
+                    alpha *= real(0.5);
+                }
+            }
+        }
+        if constexpr (POLY) {
+            for (int e = li; e < T * pm; e += G) {
+                int t = e / pm, k = e - t * pm;
+                const real *Gk = grow(t, k);
+                real r0 = -hrow(t, k), sd = 0;   // the candidate's residual is r0 + alpha sd
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    const real gv = Gk[j];
+                    r0 = fma_(gv, zs[t * N + j], r0);
+                    sd = fma_(gv, at_z ? real(0) : ds[t * N + j], sd);
+                }
+                const real lk = lams[neq + t * (2 * NU + pm) + 2 * NU + k];
+                real alpha = 1;
+#pragma unroll
+                for (int kc = 0; kc < K; ++kc) {
+                    real r = fma_(alpha, sd, r0);
+                    real cp = fmax_(r, real(0));
+                    acc[kc] += fma_(lk, r, real(0.5) * rho * cp * cp);
                     alpha *= real(0.5);
                 }
             }
@@ -886,6 +999,17 @@ struct Team {
                 acc += fma_(cu, cu, cl * cl);
             }
         }
+        if constexpr (POLY) {
+            for (int e = li; e < T * pm; e += G) {
+                int t = e / pm, k = e - t * pm;
+                const real *Gk = grow(t, k);
+                real r = -hrow(t, k);
+#pragma unroll
+                for (int j = 0; j < N; ++j) r = fma_(Gk[j], zs[t * N + j], r);
+                const real cp = r > 0 ? r : real(0);
+                acc = fma_(cp, cp, acc);
+            }
+        }
         return team_sum<G>(acc);
     }
 
@@ -896,7 +1020,7 @@ struct Team {
         for (int e = li; e < T * NU; e += G) {
             int t = e / NU, j = e - t * NU;
             real u = zs[t * N + NX + j];
-            int ru = neq + t * (2 * NU + XR) + j, rl = ru + NU;
+            int ru = neq + t * (2 * NU + XR + (POLY ? pm : 0)) + j, rl = ru + NU;
             real a = fma_(rho, u - uhi(t, j), lams[ru]);
             real c = fma_(rho, -u + ulo(t, j), lams[rl]);
             lams[ru] = a < 0 ? real(0) : a;
@@ -906,11 +1030,23 @@ struct Team {
             for (int e = li; e < T * NX; e += G) {
                 int t = e / NX, i = e - t * NX;
                 real x = zs[t * N + i];
-                int ru = neq + t * (2 * NU + XR) + 2 * NU + i, rl = ru + NX;
+                int ru = neq + t * (2 * NU + XR + (POLY ? pm : 0)) + 2 * NU + i, rl = ru + NX;
                 real a = fma_(rho, x - xhi(t, i), lams[ru]);
                 real c = fma_(rho, -x + xlo(t, i), lams[rl]);
                 lams[ru] = a < 0 ? real(0) : a;
                 lams[rl] = c < 0 ? real(0) : c;
+            }
+        }
+        if constexpr (POLY) {
+            for (int e = li; e < T * pm; e += G) {
+                int t = e / pm, k = e - t * pm;
+                const real *Gk = grow(t, k);
+                real r = -hrow(t, k);
+#pragma unroll
+                for (int j = 0; j < N; ++j) r = fma_(Gk[j], zs[t * N + j], r);
+                const int row = neq + t * (2 * NU + pm) + 2 * NU + k;
+                const real a = fma_(rho, r, lams[row]);
+                lams[row] = a < 0 ? real(0) : a;
             }
         }
         wave_sync();

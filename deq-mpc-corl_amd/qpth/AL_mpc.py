@@ -71,11 +71,12 @@ class _Launcher:
     site states only what differs (al_iter, max_newton, flags, skip, newton_counts, workspace / variant). Also here:
     the backend's capabilities, each probed once with one default, and the scratch the launches share."""
 
-    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once, xbnd=None):
+    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once, xbnd=None, poly=None):
         self.be, self.st, self.dims, self.Qd, self.q, self.F, self.c = be, st, dims, Qd, q, F, c
         self.linearize_once = linearize_once   # F, c are the linearisation frozen at the warm start
         self.dense = Qd.dim() == 4             # Qd is all of C [B,T,n,n] (MPC(diag_cost=False)): solve_lin_dense, team kernel
         self.xbnd = xbnd                       # (xlo, xhi, sb_x, st_x) of MPC(x_lower=, x_upper=): solve_lin_xbox, team kernel
+        self.poly = poly                       # (G, h, m, sb_g, st_g, sb_h, st_h) of MPC(ineqG=, ineqh=): solve_lin_poly, team kernel
         self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
         self.has_backward_ws = hasattr(be, "backward_ws")
         self.has_solve_nonlin = hasattr(be, "solve_nonlin")
@@ -104,6 +105,10 @@ class _Launcher:
             return self.be.solve_lin_xbox(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, *self.xbnd, st.z,
                                           st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
                                           **self._out, **kw)
+        if self.poly is not None:
+            return self.be.solve_lin_poly(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, *self.poly, st.z,
+                                          st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
+                                          **self._out, **kw)
         solve = self.be.solve_lin_dense if self.dense else self.be.solve_lin
         return solve(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, st.z, st.lam, st.rho,
                      self.phi, info=self.info if info else None, n_ls=N_LS, **self._out, **kw)
@@ -117,7 +122,7 @@ class _Launcher:
         dtype, and nothing between this solve's launches (dx / dx_jac included) may make it grow its cache."""
         on = self.private_kw if private else {}
         wsx = on.get("workspace")
-        if wsx is None and self.cached_ws is not None and not self.dense and self.xbnd is None:   # (no quad kernel reads a dense cost or state-bound rows)
+        if wsx is None and self.cached_ws is not None and not self.dense and self.xbnd is None and self.poly is None:   # (no quad kernel reads a dense cost, state-bound or general rows)
             if self._cached is None:
                 self._cached = self.cached_ws(self.dims, self.st.z)[0]
             wsx = self._cached
@@ -170,12 +175,20 @@ class _ALSolve(torch.autograd.Function):
     State bounds (``MPC(x_lower=, x_upper=)``): nothing changes here. The saved factor is that of the last Newton step's
     H, whose diagonal holds rho for every state-bound row active there, so w is taken with the active set held fixed,
     the approximation the control-bound rows already make.
+
+    General rows (``MPC(ineqG=, ineqh=)``): the same holds, the active rows' rho G_k' G_k being in the saved factor. When
+    ``ineqh`` requires grad it is one more input, behind ``dyn``: the rows enter g as G_k' (lam_k + rho max(G_k z - h_k, 0)),
+    so with the active set and the multipliers held fixed dh[b,t,k] = -rho_last [G_k z_final,t - h_k >= 0] (G_k . w_t),
+    formed here in PyTorch from w = q_grad and reduced over the axes ``ineqh`` broadcast over.
     """
 
     @staticmethod
-    def forward(ctx, Qd, q, st, *dyn):
+    def forward(ctx, Qd, q, st, *extra):
         mpc = st.mpc
-        need_grad = Qd.requires_grad or q.requires_grad or any(t.requires_grad for t in dyn)
+        n_h = 1 if len(extra) in (1, 4) else 0   # extra = [F, f, x0] [ineqh]
+        dyn = extra[:len(extra) - n_h]
+        ctx.n_h, ctx.poly = n_h, None
+        need_grad = Qd.requires_grad or q.requires_grad or any(t.requires_grad for t in extra)
         with torch.no_grad():
             saved = mpc._run(st, Qd.detach().contiguous(), q.detach().contiguous(), need_grad)
         ctx.mpc = mpc
@@ -189,6 +202,10 @@ class _ALSolve(torch.autograd.Function):
             lam_eq = ()
             if dyn and dyn[0].requires_grad:   # only dF reads the multipliers
                 lam_eq = (st.lam[:, :(mpc.T - 1) * mpc.n_state].clone(),)
+            if n_h:
+                B = st.z.shape[0]
+                G, h = mpc._poly_full(B, st.z.dtype, st.z.device)
+                ctx.poly = (G, h, tuple(extra[-1].shape), extra[-1].dtype)
             ctx.save_for_backward(factor, F_last, rho_last, st.z, *lam_eq)
         ctx.dims = (st.z.shape[0], mpc.T, mpc.n_state, mpc.n_ctrl)
         return st.z.clone()
@@ -196,13 +213,13 @@ class _ALSolve(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gz):
         if not ctx.has_factor:
-            return (None,) * (3 + ctx.n_dyn)
+            return (None,) * (3 + ctx.n_dyn + ctx.n_h)
         factor, F_last, rho_last, z_final, *lam_eq = ctx.saved_tensors
         gbar = gz.to(z_final.dtype).contiguous()
         q_grad = torch.empty_like(z_final)
         Qd_grad = torch.empty_like(z_final)
         kw, outs = {}, ()
-        want = ctx.needs_input_grad[3:]
+        want = ctx.needs_input_grad[3:3 + ctx.n_dyn]
         if any(want):
             from deq_mpc_corl_amd.backend import DynGrads
             B, T, nx, nu = ctx.dims
@@ -217,12 +234,22 @@ class _ALSolve(torch.autograd.Function):
         if ctx.dense:
             wz = q_grad.unsqueeze(-1) * z_final.unsqueeze(-2)
             Qd_grad = 0.5 * (wz + wz.transpose(-1, -2))
+        dh = ()
+        if ctx.n_h:
+            dh = (None,)
+            if ctx.poly is not None and ctx.needs_input_grad[-1]:
+                G, h, shape, hdt = ctx.poly
+                act = (torch.einsum("btkj,btj->btk", G, z_final) - h >= 0).to(z_final.dtype)
+                full = -rho_last.reshape(-1, 1, 1) * act * torch.einsum("btkj,btj->btk", G, q_grad)
+                if len(shape) < 3:   # ineqh was [m] or [T,m]: every instance (and stage) it was broadcast over adds up
+                    full = full.sum(dim=tuple(range(3 - len(shape))))
+                dh = (full.reshape(shape).to(hdt),)
         if not ctx.n_dyn:
-            return Qd_grad, q_grad, None
+            return (Qd_grad, q_grad, None, *dh)
         if not outs:
             outs = (None,) * 3
         return (Qd_grad, q_grad, None,
-                *(None if g is None else g.to(d) for g, d in zip(outs, ctx.dyn_dtypes)))
+                *(None if g is None else g.to(d) for g, d in zip(outs, ctx.dyn_dtypes)), *dh)
 
 
 class MPC(Module):
@@ -248,6 +275,15 @@ class MPC(Module):
     [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower]. LinDx routes only (the fused team kernel, at any
     batch): not with a callable ``dx``, ``linearize_once``, ``state_estimator``, ``Obstacle_MPC`` or ``diag_cost=False``.
     All gradients above stay available, taken with the active set held fixed.
+
+    ``ineqG`` / ``ineqh`` (both or neither): m >= 1 general linear rows G_t tau_t <= h_t per stage, on all
+    T stages next to the control bounds. ``ineqG`` is [m,n], [T,m,n] or [B,T,m,n], ``ineqh`` [m], [T,m] or [B,T,m]
+    (independently); a non-finite ``ineqh`` entry means "no row". The reference carries the two arguments, but the code
+    that reads them is never called (AL_mpc.py:496-498). ``lamda_prev`` is then [B, T nx + T (2 nu + m)]: the equality
+    rows, then per stage [u - u_upper | -u + u_lower | G_t tau_t - h_t]. LinDx routes only, like the state bounds, and not
+    together with them (a state box is 2 nx rows of G). The gradients above stay available, and the solve is also
+    differentiable w.r.t. ``ineqh`` (active set held fixed); an ``ineqG`` that requires grad raises
+    ``NotImplementedError``.
     """
 
     def __init__(self, n_state, n_ctrl, T, u_lower=None, u_upper=None, u_init=None, x_init=None,
@@ -261,9 +297,8 @@ class MPC(Module):
         super().__init__()
         if (u_lower is None) != (u_upper is None) or u_lower is None:
             raise ValueError("MPC: u_lower and u_upper are both required (AL_mpc.py:145,152)")
-        if add_goal_constraint or ineqG is not None:
-            raise NotImplementedError("goal constraints / general inequalities are "
-                                      "not reachable from Tracking_MPC and are not built")
+        if add_goal_constraint:
+            raise NotImplementedError("goal constraints are not reachable from Tracking_MPC and are not built")
         if not diag_cost and state_estimator:
             raise NotImplementedError("MPC: diag_cost=False with state_estimator: that variant runs on the "
                                       "nonlinear-caller kernels, which read diag(C)")
@@ -279,8 +314,39 @@ class MPC(Module):
             if not diag_cost:
                 raise NotImplementedError("MPC: x_lower / x_upper with diag_cost=False: no kernel instance takes "
                                           "both the dense cost and the state-bound rows")
+        if ineqG is not None or ineqh is not None:
+            # the general rows live in the fused team kernel of the LinDx routes alone (alqp_solve_lin_poly)
+            if not diag_cost:   # (before anything is asked of ineqG's shape or of ineqh)
+                raise NotImplementedError("MPC: ineqG / ineqh with diag_cost=False: no kernel instance takes both the "
+                                          "dense cost and the general rows")
+            if ineqG is None or ineqh is None:
+                raise ValueError("MPC: ineqG and ineqh go together")
+            if state_estimator:
+                raise NotImplementedError("MPC: ineqG / ineqh with state_estimator: that variant runs on the "
+                                          "nonlinear-caller kernels, which know no general rows")
+            if x_lower is not None:
+                raise NotImplementedError("MPC: ineqG / ineqh with x_lower / x_upper: no kernel instance takes both; write "
+                                          "the state box as rows of ineqG (G = [I 0; -I 0], h = [x_upper; -x_lower])")
+            ineqG, ineqh = torch.as_tensor(ineqG), torch.as_tensor(ineqh)
+            if ineqG.requires_grad:
+                raise NotImplementedError("MPC: a gradient w.r.t. ineqG is not built (it needs the multiplier estimate of "
+                                          "the last Newton step, which the one-launch routes do not return); ineqh has one")
+            n = n_state + n_ctrl
+            if ineqG.dim() not in (2, 3, 4) or ineqG.shape[-1] != n or (ineqG.dim() >= 3 and ineqG.shape[-3] != T):
+                raise ValueError(f"MPC: ineqG must be [m,n], [T,m,n] or [B,T,m,n] with n = {n}, T = {T}, got {tuple(ineqG.shape)}")
+            m = ineqG.shape[-2]
+            if ineqh.dim() not in (1, 2, 3) or ineqh.shape[-1] != m or (ineqh.dim() >= 2 and ineqh.shape[-2] != T):
+                raise ValueError(f"MPC: ineqh must be [m], [T,m] or [B,T,m] with m = {m}, T = {T}, got {tuple(ineqh.shape)}")
+            if not 1 <= m <= 64:
+                raise ValueError(f"MPC: ineqG has {m} rows per stage, the kernel takes 1 to 64")
         self.dtype = dtype
         self.n_state, self.n_ctrl, self.T = n_state, n_ctrl, T
+        self.ineqG = self.ineqh = None
+        self.n_rows = 0
+        if ineqG is not None:
+            self.ineqG = ineqG.detach().to(dtype)
+            self.ineqh = ineqh   # as given: it may require grad (_ALSolve); the solve reads _poly()'s finite copy
+            self.n_rows = int(ineqG.shape[-2])
         self.u_lower = _detach_maybe(torch.as_tensor(u_lower).to(dtype))
         self.u_upper = _detach_maybe(torch.as_tensor(u_upper).to(dtype))
         self.x_lower = self.x_upper = None
@@ -306,6 +372,7 @@ class MPC(Module):
         self.nineq = 0 if self.state_estimator else 2 * n_ctrl * T
         if self.x_lower is not None:
             self.nineq += 2 * n_state * T   # AL_mpc.py:198-201
+        self.nineq += self.n_rows * T       # AL_mpc.py:202-203
         self.rho_prev = 1.0
         self.rho_max = 1e8
         self.dyn_res_prev = 1000000
@@ -535,6 +602,27 @@ class MPC(Module):
             return lo.reshape(-1).expand(nx).contiguous(), hi.reshape(-1).expand(nx).contiguous(), 0, 0
         return lo.expand(B, self.T, nx).contiguous(), hi.expand(B, self.T, nx).contiguous(), self.T * nx, nx
 
+    def _poly(self, B, dtype, device):
+        """(G, h, m, sb_g, st_g, sb_h, st_h) as alqp_solve_lin_poly takes them, or None without general rows. A non-finite
+        entry of ineqh is "no row": a right-hand side no stage reaches, inert for every rho <= rho_max."""
+        if self.ineqG is None:
+            return None
+        m, n, T = self.n_rows, self.n_state + self.n_ctrl, self.T
+        G = self.ineqG.to(device=device, dtype=dtype).contiguous()
+        h = torch.nan_to_num(self.ineqh.detach().to(device=device, dtype=dtype), nan=SE_NO_BOUND, posinf=SE_NO_BOUND,
+                             neginf=-SE_NO_BOUND).contiguous()
+        for t, lead in ((G, G.dim() - 2), (h, h.dim() - 1)):
+            if lead == 2 and t.shape[0] != B:
+                raise ValueError(f"MPC: ineqG / ineqh given per instance for a batch of {t.shape[0]}, the solve has {B}")
+        sg = {2: (0, 0), 3: (0, m * n), 4: (T * m * n, m * n)}[G.dim()]
+        sh = {1: (0, 0), 2: (0, m), 3: (T * m, m)}[h.dim()]
+        return (G, h, m, *sg, *sh)
+
+    def _poly_full(self, B, dtype, device):
+        """The rows as [B,T,m,n] and [B,T,m] (views), as the solve read them."""
+        G, h = self._poly(B, dtype, device)[:2]
+        return G.expand(B, self.T, self.n_rows, G.shape[-1]), h.expand(B, self.T, self.n_rows)
+
     def _rho_tensor(self, B, dtype, device):
         r = self.rho_prev
         if not torch.is_tensor(r):
@@ -612,7 +700,7 @@ class MPC(Module):
         st.lin = self._as_lindx(dx, B)
         st.stream_mode = stream_mode
         st.status_flag = False
-        z = _ALSolve.apply(Qd.to(dt), q.to(dt), st, *self._dyn_inputs(st, x0, stream_mode))
+        z = _ALSolve.apply(Qd.to(dt), q.to(dt), st, *self._dyn_inputs(st, x0, stream_mode), *self._h_input())
         self.lamda_prev = st.lam[:, :self.neq].contiguous() if self.state_estimator else st.lam
         self.rho_prev = st.rho.reshape(B, 1)
         self.just_initialized = False
@@ -636,6 +724,12 @@ class MPC(Module):
             raise NotImplementedError(f"MPC: a gradient w.r.t. LinDx needs f as [B,T-1,nx]={tuple(F.shape[:3])} "
                                       f"(no broadcast over the batch), got {tuple(f.shape)}")
         return F, f, x0
+
+    def _h_input(self):
+        """(ineqh,) as an input of the autograd node when it asks for a gradient (_ALSolve), else ()."""
+        if self.ineqh is None or not torch.is_grad_enabled() or not self.ineqh.requires_grad:
+            return ()
+        return (self.ineqh,)
 
     def _linearize(self, st, z):
         """dx_jac at every (x_t, u_t), t < T-1 -> (f(z) [B,T-1,nx], F = [A|B] [B,T-1,nx,n]).
@@ -859,6 +953,21 @@ class MPC(Module):
             if st.lam.shape[1] != self.neq + self.nineq:
                 raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the state bounds need "
                                  f"{self.neq + self.nineq} = T nx + T (2 nu + 2 nx)")
+        if self.ineqG is not None:
+            # the general rows live in the fused team kernel alone (alqp_solve_lin_poly): the launch-per-step helper
+            # kernels, k_newton_step* and the compiled-in models know no such rows
+            if self._has_extra_rows():
+                raise NotImplementedError("MPC: ineqG / ineqh with obstacle rows (Obstacle_MPC): those run on the "
+                                          "nonlinear-caller kernels, which know no general rows")
+            if self.linearize_once:
+                raise NotImplementedError("MPC: ineqG / ineqh with linearize_once: the frozen-linearisation route "
+                                          "evaluates merit and dual update with kernels that know no general rows")
+            if st.lin is None:
+                raise NotImplementedError("MPC: ineqG / ineqh need affine dynamics given as LinDx(F, f): the "
+                                          "nonlinear-caller kernels and the compiled-in models know no general rows")
+            if st.lam.shape[1] != self.neq + self.nineq:
+                raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the general rows need "
+                                 f"{self.neq + self.nineq} = T nx + T (2 nu + m)")
         if self.state_estimator:
             # cost gradient on the states only (al_utils_se.py:300-310) while the Hessian keeps diag(Q) on the
             # controls (:66-68): the kernels' `state_estimator` flag. Their merit still counts the controls' cost
@@ -891,10 +1000,12 @@ class MPC(Module):
         elif st.lin is not None:
             F = st.lin[0].detach().to(device=dev, dtype=dt).contiguous()
             c = st.lin[1].detach().to(device=dev, dtype=dt).contiguous()
-        L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once, self._xbounds(B, dt, dev))
+        L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once, self._xbounds(B, dt, dev),
+                      self._poly(B, dt, dev))
         # the quad kernels take the obstacle / state-estimator rows too, so their factor can stay in the records
-        # (dense cost, state bounds: team kernel, packed factor)
-        use_qws = need_grad and L.has_backward_ws and B >= L.quad_min_batch and not L.dense and L.xbnd is None
+        # (dense cost, state bounds, general rows: team kernel, packed factor)
+        use_qws = (need_grad and L.has_backward_ws and B >= L.quad_min_batch and not L.dense and L.xbnd is None
+                   and L.poly is None)
         if use_qws:
             L.qws = be.new_workspace(dims, st.z)
             L.private_kw = dict(workspace=L.qws, variant="quad")

@@ -37,6 +37,9 @@ class Obstacle_MPC(MPC):
         if self.x_lower is not None:
             raise NotImplementedError("Obstacle_MPC: x_lower / x_upper are not built (the obstacle rows exist in the "
                                       "nonlinear-caller kernels only, which know no state-bound rows)")
+        if self.ineqG is not None:
+            raise NotImplementedError("Obstacle_MPC: ineqG / ineqh are not built (the obstacle rows exist in the "
+                                      "nonlinear-caller kernels only, which know no general rows)")
         if n_state < 3:
             raise ValueError("Obstacle_MPC: the obstacle rows act on the position x[0:3] (al_utils.py:316)")
         self.n_obstacles = 40                   # AL_mpc_custom.py:52

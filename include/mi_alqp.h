@@ -211,6 +211,35 @@ int alqp_solve_lin_xbox_f64(const AlqpDims *dims, const AlqpParams *prm, const v
                             void *stream);
 
 /*
+ * The same solve with m GENERAL LINEAR ROWS G_t z_t <= h_t per stage, z_t = [x_t; u_t], on all T stages next to the
+ * control bounds (1 <= m <= 64, a run-time number). G: [m][n] shared by every instance and stage (sb_g = st_g = 0),
+ * [T][m][n] per stage (0, m n) or [B][T][m][n] per instance (T m n, m n); h likewise without the [n] (sb_h, st_h: 0, 0 /
+ * 0, m / T m, m), independently of G. Entries must be finite: "no row" is a right-hand side no stage reaches whose
+ * product with the largest rho stays finite (the host uses 1e20). The reference carries ineqG / ineqh but never calls
+ * the code that reads them (AL_mpc.py:496-498) and cannot run this case.
+ * lam is [B][M] with M = T nx + T (2 nu + m): the T nx equality rows as everywhere, then per stage
+ * [u - u_hi | -u + u_lo | G_t z_t - h_t]. Conventions of the control rows: for r = G_k z_t - h_k, Hessian term
+ * rho G_k' G_k where r >= 0, gradient and merit terms max(r, 0), dual update max(0, lam + rho r).
+ * Team kernel only: no workspace; AlqpParams.variant must be 0 or 1 (ALQP_E_BADARG otherwise, as for a null G or h and
+ * an m outside 1..64); ALQP_E_UNSUPPORTED when (nx, nu) is no compiled instance or the horizon's LDS image does not fit:
+ * alqp_lds_bytes plus alqp_qps_per_wave * 2 * ((m + 3) & ~3) words. Flags, skip_flag and trace as
+ * alqp_solve_lin_dense_*. factor_out is the packed factor alqp_backward_* takes unchanged (the active rows' rank-one
+ * terms are in it: the active set is held fixed in the backward pass).
+ */
+int alqp_solve_lin_poly_f32(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                            const void *F, const void *c, const void *x0, const void *u_lo,
+                            const void *u_hi, long sb_u, long st_u, const void *G, const void *h, int m,
+                            long sb_g, long st_g, long sb_h, long st_h, void *z, void *lam, void *rho,
+                            void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,
+                            const AlqpTrace *trace, void *stream);
+int alqp_solve_lin_poly_f64(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                            const void *F, const void *c, const void *x0, const void *u_lo,
+                            const void *u_hi, long sb_u, long st_u, const void *G, const void *h, int m,
+                            long sb_g, long st_g, long sb_h, long st_h, void *z, void *lam, void *rho,
+                            void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,
+                            const AlqpTrace *trace, void *stream);
+
+/*
  * One Newton direction for the nonlinear-caller mode: the caller evaluated
  * dx_jac(x,u) -> (xnext, F) in PyTorch (al_utils.py:233-248). Replaces
  * merit_grad_hessian (:80-123) + cholesky_ex/cholesky_solve (:510-515).
