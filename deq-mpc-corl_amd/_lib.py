@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_ALQP_LIB") or os.path.join(_HERE, "csrc", "libmi_alqp.so")   # MI_ALQP_LIB: A/B experiments with a second build of the same ABI
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class AlqpDims(C.Structure):
@@ -81,6 +81,10 @@ _SIGS = {
     "alqp_solve_lin": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), _P, _P, _P, _P, _P, _P, _P,
                                  C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
                                  C.POINTER(AlqpTrace), _P, C.c_size_t, _P]),
+    "alqp_solve_lin_shared": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), _P, _P, _P, _P,
+                                        C.c_long, C.c_long, C.c_long, C.c_long, _P, _P, _P,
+                                        C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        C.POINTER(AlqpTrace), _P, C.c_size_t, _P]),
     "alqp_solve_lin_dense": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), _P, _P, _P, _P, _P, _P, _P,
                                        C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
                                        C.POINTER(AlqpTrace), _P]),

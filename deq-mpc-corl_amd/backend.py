@@ -168,6 +168,31 @@ class HipBackend:
         newton_counts (int32 [al_iter], device): with it the reference's batch-global exit test of the Newton loop
         runs INSIDE the launch (ALQP_EXIT_IN_KERNEL, one cooperative launch); returns False - nothing launched - when
         the grid cannot be co-resident (the caller then takes the launch-per-step route), True otherwise."""
+        return self._solve_lin(None, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status,
+                               factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant, workspace, skip,
+                               newton_counts, exit_tol)
+
+    def solve_lin_shared(self, dims, Qd, q, F, c, sb_F, st_F, sb_c, st_c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,
+                         rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
+                         n_ls=20, flags=_lib.ALQP_INIT_MERIT | _lib.ALQP_DUAL_UPDATE, rho_scale=10.0,
+                         trace=None, variant=None, workspace=None, skip=None, newton_counts=None, exit_tol=1e-3):
+        """solve_lin on batch-shared dynamics (alqp_solve_lin_shared): F and c addressed with an instance stride and a
+        stage stride in words. F [nx,n] (sb_F = st_F = 0), [T-1,nx,n] (0, nx n) or [B,T-1,nx,n] ((T-1) nx n, nx n); c
+        likewise without the last axis (0, 0 / 0, nx / (T-1) nx, nx), independently of F. Keywords, kernel choice,
+        workspace and return value as solve_lin; the numbers are those of solve_lin on the expanded tensors, bit for bit."""
+        B, T, nx, nu = dims
+        for t, name, sb, st, w in ((F, "F", sb_F, st_F, nx * (nx + nu)), (c, "c", sb_c, st_c, nx)):
+            if t is not None and min(sb, st) >= 0 and t.numel() < (B - 1) * sb + (T - 2) * st + w:
+                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
+        return self._solve_lin((sb_F, st_F, sb_c, st_c), dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,
+                               rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant,
+                               workspace, skip, newton_counts, exit_tol)
+
+    def _solve_lin(self, strides, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status,
+                   factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant, workspace, skip, newton_counts,
+                   exit_tol):
+        """solve_lin (strides None: alqp_solve_lin) and solve_lin_shared (strides = (sb_F, st_F, sb_c, st_c):
+        alqp_solve_lin_shared), which differ in the entry point and its four stride arguments alone."""
         B, T, nx, nu = dims
         dt = z.dtype
         sfx = _dt(z)
@@ -196,17 +221,18 @@ class HipBackend:
             tr = _lib.AlqpTrace(*[
                 (trace[k].data_ptr() if trace.get(k) is not None else None)
                 for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
-        fn = getattr(self.lib, "alqp_solve_lin_" + sfx)
-        rc = fn(C.byref(d), C.byref(p), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
-                _ptr(c, "c", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
-                sb_u, st_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
-                _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
-                _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
-                _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None,
-                _ptr(ws, "workspace", dt, True), ws_bytes, _stream())
+        name = ("alqp_solve_lin_" if strides is None else "alqp_solve_lin_shared_") + sfx
+        rc = getattr(self.lib, name)(
+            C.byref(d), C.byref(p), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
+            _ptr(c, "c", dt), *(strides or ()), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
+            sb_u, st_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+            _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
+            _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
+            _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None,
+            _ptr(ws, "workspace", dt, True), ws_bytes, _stream())
         if rc == _lib.ALQP_E_COOP and newton_counts is not None:
             return False
-        _lib.check(rc, "alqp_solve_lin_" + sfx)
+        _lib.check(rc, name)
         return True
 
     def solve_lin_dense(self, dims, Cs, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,

@@ -99,19 +99,23 @@ bool set_solve(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, cons
     return true;
 }
 
-template <typename real>
+// Args: SolveArgs (alqp_solve_lin_*) or ShdynSolveArgs with its strides set by the caller (alqp_solve_lin_shared_*);
+// `team` / `quad`: the two kernel families' launchers for that type. Checks, kernel choice and workspace handling are
+// this one function for both entry points.
+template <typename real, typename Args>
 int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
                    const void *F, const void *c, const void *x0, const void *u_lo, const void *u_hi,
                    long sb_u, long st_u, void *z, void *lam, void *rho, void *phi, void *rnorm2,
                    int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
-                   void *workspace, size_t ws_bytes, void *stream) {
+                   void *workspace, size_t ws_bytes, void *stream, Args a,
+                   int (*team)(int, int, const Args &, const TraceArgs<real> *, hipStream_t),
+                   int (*quad)(int, int, const Args &, const TraceArgs<real> *, real *, hipStream_t)) {
     if (!dims_ok(dims) || !prm || !Qd || !q || !F || !c || !x0 || !u_lo || !u_hi || !z || !lam || !rho || !phi)
         return ALQP_E_BADARG;
     if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
     if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
     if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
-    SolveArgs<real> a = {};
-    if (!set_solve(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+    if (!set_solve<real>(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
         return ALQP_E_BADARG;
     a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
     a.stagger = quad_stagger(prm->quad_stagger, dims->B, dims->T, dims->nx, dims->nu, prm->al_iter * prm->max_newton, sizeof(real) == 8);
@@ -132,11 +136,34 @@ int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, 
         if (prm->flags & ALQP_SAVE_FACTOR) return ALQP_E_UNSUPPORTED;
         if (need == 0) return ALQP_E_UNSUPPORTED;
         if (!workspace || ws_bytes < need) return ALQP_E_BADARG;
-        return dispatch_solve_quad<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (real *)workspace,
-                                         (hipStream_t)stream);
+        return quad(dims->nx, dims->nu, a, trace ? &tr : nullptr, (real *)workspace, (hipStream_t)stream);
     }
     if (variant != 1) return ALQP_E_BADARG;
-    return dispatch_solve<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
+    return team(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
+}
+
+// Batch-shared dynamics: the plain solve with F and c behind an instance stride and a stage stride. Only the three
+// layouts of mi_alqp.h are taken (any other pair would be a bug in the caller, and a stride beyond the caller's tensor an
+// out-of-bounds read).
+template <typename real>
+int solve_lin_shared_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
+                          const void *c, long sb_F, long st_F, long sb_c, long st_c, const void *x0, const void *u_lo,
+                          const void *u_hi, long sb_u, long st_u, void *z, void *lam, void *rho, void *phi,
+                          void *rnorm2, int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
+                          void *workspace, size_t ws_bytes, void *stream) {
+    if (!dims_ok(dims) || !F || !c) return ALQP_E_BADARG;
+    const long wF = (long)dims->nx * (dims->nx + dims->nu), wc = dims->nx, Tm = dims->T - 1;
+    auto form_ok = [&](long sb, long st, long w) {
+        return (sb == 0 && st == 0) || (sb == 0 && st == w) || (sb == Tm * w && st == w);
+    };
+    if (sb_F < 0 || st_F < 0 || sb_c < 0 || st_c < 0 || !form_ok(sb_F, st_F, wF) || !form_ok(sb_c, st_c, wc))
+        return ALQP_E_BADARG;
+    ShdynSolveArgs<real> a = {};
+    a.sb_F = sb_F; a.sb_c = sb_c;
+    a.mt_F = st_F ? -1 : 0; a.mt_c = st_c ? -1 : 0;   // (form_ok: a stage stride is 0 or the packed one)
+    return solve_lin_impl<real, ShdynSolveArgs<real>>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi,
+                                                      rnorm2, info, status, factor_out, trace, workspace, ws_bytes, stream,
+                                                      a, dispatch_solve_shdyn<real>, dispatch_solve_quad_shdyn<real>);
 }
 
 // Dense stage cost: the team kernel only (no quad kernel reads a full C), so no workspace and variant 0 / 1 alike.
@@ -327,7 +354,7 @@ int backward_impl(const AlqpDims *dims, const void *factor, void *workspace, siz
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 15; }
+int alqp_abi_version(void) { return 16; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -396,9 +423,23 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                              void *lam, void *rho, void *phi, void *rnorm2, int *info,                \
                              unsigned char *status, void *factor_out, const AlqpTrace *trace,         \
                              void *workspace, size_t ws_bytes, void *stream) {                        \
-        return alqp::solve_lin_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, \
-                                          rho, phi, rnorm2, info, status, factor_out, trace,          \
-                                          workspace, ws_bytes, stream);                               \
+        return alqp::solve_lin_impl<REAL, alqp::SolveArgs<REAL>>(                                     \
+            dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info,       \
+            status, factor_out, trace, workspace, ws_bytes, stream, alqp::SolveArgs<REAL>{},          \
+            alqp::dispatch_solve<REAL>, alqp::dispatch_solve_quad<REAL>);                             \
+    }                                                                                                 \
+    int alqp_solve_lin_shared_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,      \
+                                    const void *q, const void *F, const void *c, long sb_F,           \
+                                    long st_F, long sb_c, long st_c, const void *x0,                  \
+                                    const void *u_lo, const void *u_hi, long sb_u, long st_u,         \
+                                    void *z, void *lam, void *rho, void *phi, void *rnorm2,           \
+                                    int *info, unsigned char *status, void *factor_out,               \
+                                    const AlqpTrace *trace, void *workspace, size_t ws_bytes,         \
+                                    void *stream) {                                                   \
+        return alqp::solve_lin_shared_impl<REAL>(dims, prm, Qd, q, F, c, sb_F, st_F, sb_c, st_c, x0,  \
+                                                 u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2,    \
+                                                 info, status, factor_out, trace, workspace,          \
+                                                 ws_bytes, stream);                                   \
     }                                                                                                 \
     int alqp_solve_lin_dense_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *C,        \
                                    const void *q, const void *F, const void *c, const void *x0,       \

@@ -51,6 +51,29 @@ struct PolySolveArgs : SolveArgs<real> {
     long sb_h, st_h;
 };
 
+// The fused solve on batch-shared dynamics (k_solve_lin_shdyn, k_solve_lin_quad_shdyn): F and c addressed with an
+// instance stride and a stage stride like the bounds (sb_u / st_u), again in a type of its own.
+// The stage stride of either is 0 or the packed one (nx n / nx; alqp_solve_lin_shared_* takes nothing else), so the kernels
+// get it as a mask on the packed stride: one 32-bit register each for the whole kernel instead of a 64-bit stride, and
+// 32-bit offset arithmetic. (Measured on the register-capped fp32 builds, bytes of scratch against the plain twin's: 64-bit
+// strides (10,3) 80 / 68, (12,4) 144 / 140, (8,2) 116 / 108; a mask on the stage index (10,3) 80 / 68; this form: none above.)
+template <typename real>
+struct ShdynSolveArgs : SolveArgs<real> {
+    long sb_F, sb_c;   // words from one instance's F / c to the next: 0 (shared by the batch) or (T-1) nx n / (T-1) nx
+    int mt_F, mt_c;    // -1: stage t's F / c lies t nx n / t nx words behind stage 0's; 0: one F / c for every stage
+};
+
+// Words from stage 0 to stage t of an instance's F / c, inside Team (alqp_team.hpp) and Quad (alqp_quad.hpp). The
+// shared-dynamics units (-DALQP_SHDYN_UNIT, build.sh) mask the packed stride with the struct's members mt_F / mt_c; every
+// other unit keeps the compile-time expression it always had, so its kernels compile to the same code.
+#ifdef ALQP_SHDYN_UNIT
+#define ALQP_F_STAGE(t) ((unsigned)(t) * (unsigned)((NX * N) & mt_F))   // (32 bits hold T nx n; the instance base is size_t)
+#define ALQP_C_STAGE(t) ((unsigned)(t) * (unsigned)(NX & mt_c))
+#else
+#define ALQP_F_STAGE(t) ((size_t)(t) * NX * N)
+#define ALQP_C_STAGE(t) ((t) * NX)
+#endif
+
 // sum of one value per workgroup over the whole (cooperatively launched) grid, the same bits in every lane of every
 // workgroup: partials in workgroup order, 64 interleaved chains, xor butterfly. Every workgroup must call it.
 __device__ inline double grid_sum_ordered(double block_val, double *scratch, int &phase) {

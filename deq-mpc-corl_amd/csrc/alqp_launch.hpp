@@ -24,6 +24,8 @@ template <typename real>
 inline int flags_of(const XboxSolveArgs<real> &a) { return a.flags; }
 template <typename real>
 inline int flags_of(const PolySolveArgs<real> &a) { return a.flags; }
+template <typename real>
+inline int flags_of(const ShdynSolveArgs<real> &a) { return a.flags; }
 template <typename Fn, typename A0, typename... Rest>
 int launch_maybe_coop(Fn fn, unsigned grid, size_t lds, hipStream_t stream, A0 a0, Rest... rest) {
     if (flags_of(a0) & ALQP_EXIT_IN_KERNEL) {
@@ -72,12 +74,17 @@ int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const Trac
 template <typename real>
 int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
+int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
+template <typename real>
 size_t lds_query(int nx, int nu, int T);   // bytes of the team LDS image, 0: no such instance
 
 // alqp_quad.hip
 template <typename real>
 int dispatch_solve_quad(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, real *ws,
                         hipStream_t stream);
+template <typename real>
+int dispatch_solve_quad_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, real *ws,
+                              hipStream_t stream);
 template <typename real, bool DYN>
 int dispatch_backward_quad(int nx, int nu, const BwdArgs<real, DYN> &a, real *ws, hipStream_t stream);
 template <typename real>

@@ -1,6 +1,6 @@
 // alqp_quad.hip - the quad kernels (4 lanes per QP, registers + DPP, HBM workspace: alqp_quad.hpp) and their
 // launchers. Compiled once per dtype (-DALQP_QUAD_F32 / -DALQP_QUAD_F64), one object each.
-#ifdef ALQP_BWD_DYN_UNIT
+#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_SHDYN_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -30,8 +30,16 @@ __device__ unsigned long long g_phase_cycles[10];
 // the nonlinear solve with that model inlined (alqp_solve_nonlin): every Newton step re-linearises
 // on the device, the line search and the dual update use the true dynamics; a.F then points at the
 // F region of the workspace (behind the records) and a.c is unused.
+// The shared-dynamics units (-DALQP_SHDYN_UNIT, one per dtype) compile this same body as k_solve_lin_quad_shdyn, NoDyn only:
+// F and c addressed through an instance stride and a stage stride (a.sb_F / a.mt_F, a.sb_c / a.mt_c; ALQP_F_STAGE /
+// ALQP_C_STAGE in Quad). Two headers over one body, as in alqp_team.hip, and for the same reason.
+#ifdef ALQP_SHDYN_UNIT
+template <typename real, int NX, int NU, bool TRACE, class Dyn = NoDyn>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_solve_lin_quad_shdyn(ShdynSolveArgs<real> a, TraceArgs<real> tr, real *ws) {
+#else
 template <typename real, int NX, int NU, bool TRACE, class Dyn = NoDyn>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_solve_lin_quad(SolveArgs<real> a, TraceArgs<real> tr, real *ws) {
+#endif
     using C = QCfg<real, NX, NU>;
     constexpr bool NL = Dyn::ID != 0;
     // fp64 is short of registers already: its line search keeps a pass of its own
@@ -83,8 +91,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     qd.active = active;
     qd.gQd = a.Qd + (size_t)b * T * N;
     qd.gq = a.q + (size_t)b * T * N;
+#ifdef ALQP_SHDYN_UNIT
+    qd.gF = a.F + (size_t)b * a.sb_F;
+    qd.gc = a.c + (size_t)b * a.sb_c;
+    qd.mt_F = a.mt_F; qd.mt_c = a.mt_c;
+#else
     qd.gF = a.F + (size_t)b * (T - 1) * NX * N;
     qd.gc = a.c + (size_t)b * (T - 1) * NX;
+#endif
     qd.gx0 = a.x0 + (size_t)b * NX;
     qd.gulo = a.ulo + (size_t)b * a.sb_u;
     qd.guhi = a.uhi + (size_t)b * a.sb_u;
@@ -367,6 +381,16 @@ int launch_quad_kernel(Fn fn, int B, hipStream_t stream, Args... args) {
     return launch_maybe_coop(fn, grid, 0, stream, args...);
 }
 
+#ifdef ALQP_SHDYN_UNIT
+template <typename real>
+int dispatch_solve_quad_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, real *ws,
+                              hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (tr) return launch_quad_kernel<real, NX, NU>(k_solve_lin_quad_shdyn<real, NX, NU, true>, a.B, stream, a, *tr, ws);
+        return launch_quad_kernel<real, NX, NU>(k_solve_lin_quad_shdyn<real, NX, NU, false>, a.B, stream, a, TraceArgs<real>{}, ws);
+    });
+}
+#else
 template <typename real>
 int dispatch_solve_quad(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, real *ws,
                         hipStream_t stream) {
@@ -407,6 +431,7 @@ int dispatch_step_quad(int nx, int nu, const StepArgs<real> &a, real *ws, hipStr
         return launch_quad_kernel<real, NX, NU>(k_newton_step_quad<real, NX, NU>, a.B, stream, a, ws);
     });
 }
+#endif
 
 #ifdef ALQP_QUAD_F32
 using quad_real = float;
@@ -415,7 +440,10 @@ using quad_real = double;
 #endif
 // The DYN instantiations of k_backward_quad are a compile unit of their own per dtype (-DALQP_BWD_DYN_UNIT, build.sh): the
 // unit every other quad kernel comes out of then holds exactly the instantiations it held before they existed.
-#ifndef ALQP_BWD_DYN_UNIT
+// So are the shared-dynamics instantiations of the fused solve (-DALQP_SHDYN_UNIT).
+#if defined(ALQP_SHDYN_UNIT)
+template int dispatch_solve_quad_shdyn<quad_real>(int, int, const ShdynSolveArgs<quad_real> &, const TraceArgs<quad_real> *, quad_real *, hipStream_t);
+#elif !defined(ALQP_BWD_DYN_UNIT)
 template int dispatch_solve_quad<quad_real>(int, int, const SolveArgs<quad_real> &, const TraceArgs<quad_real> *, quad_real *, hipStream_t);
 template int dispatch_backward_quad<quad_real, false>(int, int, const BwdArgs<quad_real, false> &, quad_real *, hipStream_t);
 template int dispatch_solve_nonlin<quad_real>(int, int, int, const SolveArgs<quad_real> &, quad_real *, hipStream_t);

@@ -326,6 +326,9 @@ struct Quad {
     bool active;
     const real *gQd, *gq, *gF, *gc, *gx0, *gulo, *guhi;
     long st_u;
+#ifdef ALQP_SHDYN_UNIT
+    int mt_F, mt_c;   // k_solve_lin_quad_shdyn only: masks on the stage stride of F / c, -1 per stage or 0 shared (ALQP_F_STAGE, ALQP_C_STAGE)
+#endif
     real *gz, *glam, *rec;
     real rho;
     int info;
@@ -494,7 +497,7 @@ struct Quad {
     // index clamped, result masked) so that all of a stage's loads go out in one batch:
     // a load inside a divergent branch cannot be hoisted and costs its own round trip.
     __device__ __forceinline__ void load_F_rows(int t, WT &W) const {
-        const real *Fg = gF + (size_t)t * NX * N;
+        const real *Fg = gF + ALQP_F_STAGE(t);
 #pragma unroll
         for (int s = 0; s < SW; ++s) {
             const int r = 4 * s + q;
@@ -549,7 +552,7 @@ struct Quad {
                     const bool has = ju < NU;
                     st_own_us(rp, has ? a0 : real(0), has ? a1 : real(0), has ? a2 : real(0), has ? a3 : real(0));
                 }
-                if (dyn && have_c) ld_own_ext<NX>(gc + t * NX, vx);
+                if (dyn && have_c) ld_own_ext<NX>(gc + ALQP_C_STAGE(t), vx);
                 else {
 #pragma unroll
                     for (int s = 0; s < SW; ++s) vx[s] = 0;
@@ -567,7 +570,7 @@ struct Quad {
                     const int r = 4 * s + q;
                     rr[s] = 0;
                     if (4 * s + 3 < NX || r < NX) {
-                        real xn = dyn ? gc[t * NX + r] : real(0);
+                        real xn = dyn ? gc[ALQP_C_STAGE(t) + r] : real(0);
 #pragma unroll
                         for (int k = 0; k < N; ++k) xn = fma_(W[s][k], zt[k], xn);
                         // row block T-1 holds the initial-state rows x_0 - x_init (al_utils.py:274)

@@ -1,6 +1,7 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
-#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT) || defined(ALQP_POLY_UNIT)
+#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT) || defined(ALQP_POLY_UNIT) || \
+    defined(ALQP_SHDYN_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -34,6 +35,10 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // control rows (Team's POLY flag), rows and right-hand sides at a.G / a.h. Its LDS image is the team image plus a hand-over
 // region of 2 pad4(a.m) words per team. Uncapped builds only, for the reason given above: a capped build spills, and a
 // spilling build of this body is what the TRACE paragraph describes.
+// The shared-dynamics unit (-DALQP_SHDYN_UNIT), a fifth header: k_solve_lin_shdyn, the plain problem with F and c addressed
+// through an instance stride and a stage stride (a.sb_F / a.mt_F, a.sb_c / a.mt_c; ALQP_F_STAGE / ALQP_C_STAGE in Team), so
+// that one F, or one sequence F_t, serves the whole batch. Same arithmetic in the same order on the same values as
+// k_solve_lin; capped and uncapped builds chosen by the plain kernel's rule (dispatch_solve_shdyn).
 #if defined(ALQP_DENSE_UNIT)
 template <typename real, int NX, int NU, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_dense(DenseSolveArgs<real> a, TraceArgs<real> tr) {
@@ -46,6 +51,10 @@ __global__ __launch_bounds__(64, 1) void k_solve_lin_xbox(XboxSolveArgs<real> a,
 template <typename real, int NX, int NU, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_poly(PolySolveArgs<real> a, TraceArgs<real> tr) {
     constexpr bool DENSE = false, XBOX = false, POLY = true;
+#elif defined(ALQP_SHDYN_UNIT)
+template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
+__global__ __launch_bounds__(64, OCC) void k_solve_lin_shdyn(ShdynSolveArgs<real> a, TraceArgs<real> tr) {
+    constexpr bool DENSE = false, XBOX = false, POLY = false;
 #else
 template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
 __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceArgs<real> tr) {
@@ -80,8 +89,14 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.gQd = a.Qd + (size_t)b * T * N;
 #endif
     tm.gq = a.q + (size_t)b * T * N;
+#ifdef ALQP_SHDYN_UNIT
+    tm.gF = a.F + (size_t)b * a.sb_F;
+    tm.gc = a.c + (size_t)b * a.sb_c;
+    tm.mt_F = a.mt_F; tm.mt_c = a.mt_c;
+#else
     tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
     tm.gc = a.c + (size_t)b * (T - 1) * NX;
+#endif
     tm.gx0 = a.x0 + (size_t)b * NX;
     tm.gulo = a.ulo + (size_t)b * a.sb_u;
     tm.guhi = a.uhi + (size_t)b * a.sb_u;
@@ -392,7 +407,20 @@ inline long team_simds() {   // SIMDs of the device (4 per CU)
     return n;
 }
 
-#if !defined(ALQP_DENSE_UNIT) && !defined(ALQP_XBOX_UNIT) && !defined(ALQP_POLY_UNIT)
+#if defined(ALQP_SHDYN_UNIT)
+template <typename real>
+int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {   // dispatch_solve's occupancy rule
+        if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin_shdyn<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
+        if constexpr (sizeof(real) == 4) {
+            const long waves = (a.B + Cfg<real, NX, NU>::QPW - 1) / Cfg<real, NX, NU>::QPW;
+            if (waves > team_simds())
+                return launch_team_kernel<real, NX, NU>(k_solve_lin_shdyn<real, NX, NU, false, 2>, a.B, a.T, stream, a, TraceArgs<real>{});
+        }
+        return launch_team_kernel<real, NX, NU>(k_solve_lin_shdyn<real, NX, NU, false, 1>, a.B, a.T, stream, a, TraceArgs<real>{});
+    });
+}
+#elif !defined(ALQP_DENSE_UNIT) && !defined(ALQP_XBOX_UNIT) && !defined(ALQP_POLY_UNIT)
 template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
@@ -455,8 +483,11 @@ size_t lds_query(int nx, int nu, int T) {
 // The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
 // So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT), the state-bound ones (-DALQP_XBOX_UNIT) and
-// the general-row ones (-DALQP_POLY_UNIT).
-#if defined(ALQP_POLY_UNIT)
+// the general-row ones (-DALQP_POLY_UNIT) and the shared-dynamics ones (-DALQP_SHDYN_UNIT).
+#if defined(ALQP_SHDYN_UNIT)
+template int dispatch_solve_shdyn<float>(int, int, const ShdynSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
+template int dispatch_solve_shdyn<double>(int, int, const ShdynSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+#elif defined(ALQP_POLY_UNIT)
 template int dispatch_solve_poly<float>(int, int, const PolySolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_poly<double>(int, int, const PolySolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 #elif defined(ALQP_XBOX_UNIT)

@@ -32,6 +32,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "alqp_args.hpp"   // ALQP_F_STAGE, ALQP_C_STAGE
+
 namespace alqp {
 
 constexpr int pad4(int v) { return (v + 3) & ~3; }
@@ -230,6 +232,9 @@ struct Team {
     // problem (global memory, this instance)
     const real *gQd, *gq, *gF, *gc, *gx0, *gulo, *guhi, *gxnext;
     long st_u;
+#ifdef ALQP_SHDYN_UNIT
+    int mt_F, mt_c;   // k_solve_lin_shdyn only: masks on the stage stride of F / c, -1 per stage or 0 shared (ALQP_F_STAGE, ALQP_C_STAGE)
+#endif
     real rho;
     int info;
     // obstacle rows (Obstacle_MPC, qpth/AL_mpc_custom.py; al_utils.py:313-323, 351-388): nobs spheres per
@@ -328,7 +333,7 @@ struct Team {
     static constexpr int FCH = (NX * N + G - 1) / G;  // F words per lane
 
     __device__ void fetch_F(int t, real (&buf)[FCH]) const {
-        const real *Fg = gF + (size_t)t * NX * N;
+        const real *Fg = gF + ALQP_F_STAGE(t);
 #pragma unroll
         for (int i = 0; i < FCH; ++i) {
             int e = li + i * G;
@@ -367,7 +372,7 @@ struct Team {
                 wave_sync();                                 // runs under the previous stage's products)
                 if (t + 2 < T) fetch_F(t + 1, fbuf);
                 if (isW) {
-                    real s = gc[t * NX + wr];
+                    real s = gc[ALQP_C_STAGE(t) + wr];
                     real fv[N], zv[N];   // operands first, products after (see backward_sweep)
 #pragma unroll
                     for (int k = 0; k < N; ++k) { fv[k] = Fs[wr * N + k]; zv[k] = zs[t * N + k]; }
@@ -461,7 +466,7 @@ struct Team {
                 if (t + 1 < T && isH) { Qn = gQd[(t + 1) * N + hi]; qn = gq[(t + 1) * N + hi]; }
             }
             if (t + 2 < T && isW) {
-                cn = gxnext ? gxnext[(t + 1) * NX + wr] : gc[(t + 1) * NX + wr];
+                cn = gxnext ? gxnext[(t + 1) * NX + wr] : gc[ALQP_C_STAGE(t + 1) + wr];
                 lan = lams[(t + 1) * NX + wr];
             }
             if (t + 1 < T) {

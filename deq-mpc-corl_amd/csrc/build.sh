@@ -25,8 +25,11 @@ alqp_team_dyn      alqp_team.hip      -DALQP_BWD_DYN_UNIT
 alqp_team_dense    alqp_team.hip      -DALQP_DENSE_UNIT
 alqp_team_xbox     alqp_team.hip      -DALQP_XBOX_UNIT
 alqp_team_poly     alqp_team.hip      -DALQP_POLY_UNIT
+alqp_team_shdyn    alqp_team.hip      -DALQP_SHDYN_UNIT
 alqp_quad_dyn_f32  alqp_quad.hip      -DALQP_QUAD_F32 -DALQP_BWD_DYN_UNIT
 alqp_quad_dyn_f64  alqp_quad.hip      -DALQP_QUAD_F64 -DALQP_BWD_DYN_UNIT
+alqp_quad_shdyn_f32  alqp_quad.hip    -DALQP_QUAD_F32 -DALQP_SHDYN_UNIT
+alqp_quad_shdyn_f64  alqp_quad.hip    -DALQP_QUAD_F64 -DALQP_SHDYN_UNIT
 alqp_dyn_casadi  alqp_dyn_casadi.hip
 alqp_ipm         alqp_ipm.hip
 alqp_ipm_g4_f64  alqp_ipm_g4.hip      -DALQP_G4_F64

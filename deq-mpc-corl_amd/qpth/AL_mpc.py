@@ -71,7 +71,7 @@ class _Launcher:
     site states only what differs (al_iter, max_newton, flags, skip, newton_counts, workspace / variant). Also here:
     the backend's capabilities, each probed once with one default, and the scratch the launches share."""
 
-    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once, xbnd=None, poly=None):
+    def __init__(self, be, st, dims, Qd, q, bnd, F, c, linearize_once, xbnd=None, poly=None, shdyn=None):
         self.be, self.st, self.dims, self.Qd, self.q, self.F, self.c = be, st, dims, Qd, q, F, c
         self.linearize_once = linearize_once   # F, c are the linearisation frozen at the warm start
         self.dense = Qd.dim() == 4             # Qd is all of C [B,T,n,n] (MPC(diag_cost=False)): solve_lin_dense, team kernel
@@ -80,6 +80,17 @@ class _Launcher:
         self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
         self.has_backward_ws = hasattr(be, "backward_ws")
         self.has_solve_nonlin = hasattr(be, "solve_nonlin")
+        self.has_solve_lin_shared = hasattr(be, "solve_lin_shared")
+        # shdyn: (sb_F, st_F, sb_c, st_c) when F or c is shared by the batch (LinDx(F[T-1,nx,n] | F[nx,n]), f likewise), else
+        # None. Shared data stays as given only for the plain problem on a backend that has solve_lin_shared; for a dense
+        # cost, state bounds or general rows (their kernels read a per-instance F) and for any other backend it is
+        # materialised here, once per solve.
+        self.shdyn = shdyn
+        if shdyn is not None and (not self.has_solve_lin_shared or self.dense or xbnd is not None or poly is not None):
+            B, T, nx, nu = dims
+            self.F = F.expand(B, T - 1, nx, nx + nu).contiguous()
+            self.c = c.expand(B, T - 1, nx).contiguous()
+            self.shdyn = None
         self.can_exit_in_kernel = getattr(be, "supports_exit_in_kernel", False)
         self.quad_min_batch = getattr(be, "QUAD_MIN_BATCH", 0)   # batch from which the quad kernels are the default
         B, dt, dev = dims[0], st.z.dtype, st.z.device
@@ -109,6 +120,10 @@ class _Launcher:
             return self.be.solve_lin_poly(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, *self.poly, st.z,
                                           st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
                                           **self._out, **kw)
+        if self.shdyn is not None:
+            return self.be.solve_lin_shared(self.dims, self.Qd, self.q, self.F, self.c, *self.shdyn, *self._x0_bounds, st.z,
+                                            st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
+                                            **self._out, **kw)
         solve = self.be.solve_lin_dense if self.dense else self.be.solve_lin
         return solve(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, st.z, st.lam, st.rho,
                      self.phi, info=self.info if info else None, n_ls=N_LS, **self._out, **kw)
@@ -164,7 +179,7 @@ class _ALSolve(torch.autograd.Function):
 
     Beyond the reference, on the affine (``LinDx``) routes: when ``LinDx.F``, ``LinDx.f`` or ``x0`` requires grad they
     are the inputs ``dyn = (F, f, x0)`` and get dF, dc, dx0 of include/mi_alqp.h (alqp_backward_* with an AlqpBwdDyn) out
-    of the same w, with the same approximations (multipliers and active set held fixed, factor of the last executed Newton step);
+    of the same w (a batch-shared ``F`` / ``f`` gets the per-instance dF / dc summed over the axes it was broadcast over), with the same approximations (multipliers and active set held fixed, factor of the last executed Newton step);
     the multipliers in those formulas are the equality rows of the lam the solve returned, cloned here. With a callable
     ``dx`` nothing of this applies: ``x0.grad`` stays None there.
 
@@ -195,6 +210,7 @@ class _ALSolve(torch.autograd.Function):
         ctx.has_factor = saved is not None
         ctx.n_dyn = len(dyn)
         ctx.dyn_dtypes = tuple(t.dtype for t in dyn)
+        ctx.dyn_shapes = tuple(tuple(t.shape) for t in dyn)
         ctx.dense = Qd.dim() == 4
         if saved is not None:
             kind, factor, F_last, rho_last = saved
@@ -248,6 +264,11 @@ class _ALSolve(torch.autograd.Function):
             return (Qd_grad, q_grad, None, *dh)
         if not outs:
             outs = (None,) * 3
+        # a shared F / f ([T-1,nx,n], [nx,n] / [T-1,nx], [nx]) gets the per-instance gradient summed over the axes it was
+        # broadcast over, like ineqh above (x0 is per instance: nothing to sum)
+        full_dims = (4, 3, 2)
+        outs = tuple(g if g is None or len(sh) == fd else g.sum(dim=tuple(range(fd - len(sh))))
+                     for g, sh, fd in zip(outs, ctx.dyn_shapes, full_dims))
         return (Qd_grad, q_grad, None,
                 *(None if g is None else g.to(d) for g, d in zip(outs, ctx.dyn_dtypes)), *dh)
 
@@ -263,10 +284,17 @@ class MPC(Module):
     Differentiable w.r.t. the cost (diag C and c, as the reference). ``diag_cost=False``: C_t is a full matrix (cross
     terms, a Riccati terminal cost, a rotated frame); its symmetric part enters the solve and the gradient reaches all of
     C. That exists for affine dynamics given as ``LinDx`` only (the fused team kernel), not with a callable ``dx``,
-    ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``. With affine dynamics given as ``LinDx(F, f)`` (F
-    [B,T-1,nx,n], f [B,T-1,nx], no broadcast over the batch) the solve is also differentiable w.r.t. ``F``, ``f`` and
-    ``x0`` (see ``_ALSolve``); not on the streaming route (``NotImplementedError``). With a callable ``dx`` there are
-    no such gradients: ``x0.grad`` stays ``None``.
+    ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``. With affine dynamics given as ``LinDx(F, f)`` the solve
+    is also differentiable w.r.t. ``F``, ``f`` and ``x0`` (see ``_ALSolve``); not on the streaming route
+    (``NotImplementedError``). With a callable ``dx`` there are no such gradients: ``x0.grad`` stays ``None``.
+
+    ``LinDx(F, f)``: ``F`` is [B,T-1,nx,n] (per instance), [T-1,nx,n] (one sequence F_t for the whole
+    batch, LTV) or [nx,n] (one model for the whole batch, LTI); ``f`` is [B,T-1,nx], [T-1,nx] or [nx], independently of
+    ``F``. Shared forms are not copied B times: the kernels read the one copy (``HipBackend.solve_lin_shared``), on every
+    LinDx route, and the result equals that of the expanded tensors bit for bit. Together with ``diag_cost=False``,
+    ``x_lower`` / ``x_upper`` or ``ineqG`` / ``ineqh``, and on a backend without ``solve_lin_shared``, the shared forms are
+    accepted and MATERIALISED (B copies) on the host once per solve; so is ``F`` for the backward pass when a gradient
+    is asked for. A shared ``F`` / ``f`` that requires grad receives the sum of the per-instance gradients.
 
     ``x_lower`` / ``x_upper`` (both or neither): box constraints on the states, each a number, [nx], or
     anything that broadcasts to [B,T,nx] (per-stage bounds can relax stage 0, whose state is pinned to x0). A non-finite
@@ -480,7 +508,8 @@ class MPC(Module):
         for t in range(self.T - 1):
             xt, ut = xs[t], actions[:, t]
             if lin is not None:
-                F, c = lin
+                F = lin[0].expand(x.shape[0], self.T - 1, *lin[0].shape[-2:])   # views: a shared F / f is not copied
+                c = lin[1].expand(x.shape[0], self.T - 1, lin[1].shape[-1])
                 nxt = torch.einsum("bij,bj->bi", F[:, t].to(xt.dtype), torch.cat([xt, ut], -1)) + c[:, t].to(xt.dtype)
             else:
                 nxt = dynamics(xt, ut)
@@ -562,7 +591,9 @@ class MPC(Module):
         return bool(self.state_estimator)
 
     def _as_lindx(self, dx, B):
-        """(F[B,T-1,nx,n], c[B,T-1,nx]) if `dx` carries affine data, else None."""
+        """(F, f, (sb_F, st_F), (sb_c, st_c)) if `dx` carries affine data, else None. F is [B,T-1,nx,n], [T-1,nx,n] or
+        [nx,n], f [B,T-1,nx], [T-1,nx] or [nx]; the strides (words from one instance's / one stage's data to the next) are
+        what alqp_solve_lin_shared takes: (0, 0) for one model, (0, w) for one sequence, ((T-1) w, w) per instance."""
         if self._has_extra_rows():
             return None   # obstacle rows exist only in the nonlinear-caller building blocks
         F = getattr(dx, "F", None)
@@ -570,9 +601,17 @@ class MPC(Module):
         if F is None or c is None or not torch.is_tensor(F):
             return None
         n = self.n_state + self.n_ctrl
-        if tuple(F.shape) != (B, self.T - 1, self.n_state, n):
-            raise ValueError(f"LinDx.F must be [B,T-1,nx,n]={B, self.T - 1, self.n_state, n}, got {tuple(F.shape)}")
-        return F, c
+        Tm, nx = self.T - 1, self.n_state
+        forms_F = {(B, Tm, nx, n): (Tm * nx * n, nx * n), (Tm, nx, n): (0, nx * n), (nx, n): (0, 0)}
+        if tuple(F.shape) not in forms_F:
+            raise ValueError(f"LinDx.F must be [B,T-1,nx,n]={B, Tm, nx, n}, [T-1,nx,n]={Tm, nx, n} (shared by the batch) "
+                             f"or [nx,n]={nx, n} (shared by the batch and the stages), got {tuple(F.shape)}")
+        forms_c = {(B, Tm, nx): (Tm * nx, nx), (Tm, nx): (0, nx), (nx,): (0, 0)}
+        if not torch.is_tensor(c) or tuple(c.shape) not in forms_c:
+            raise ValueError(f"LinDx.f must be [B,T-1,nx]={B, Tm, nx}, [T-1,nx]={Tm, nx} (shared by the batch) or "
+                             f"[nx]={(nx,)} (shared by the batch and the stages), got "
+                             f"{tuple(c.shape) if torch.is_tensor(c) else type(c).__name__}")
+        return F, c, forms_F[tuple(F.shape)], forms_c[tuple(c.shape)]
 
     def _bounds(self, B, dtype, device):
         nu = self.n_ctrl
@@ -713,17 +752,14 @@ class MPC(Module):
         (_ALSolve), else (): the node, and every launch, is then exactly what it is without this feature."""
         if st.lin is None or not torch.is_grad_enabled():
             return ()
-        F, f = st.lin
+        F, f = st.lin[:2]
         if not (F.requires_grad or (torch.is_tensor(f) and f.requires_grad) or x0.requires_grad):
             return ()
         if stream_mode or self.linearize_once:
             raise NotImplementedError("MPC: gradients w.r.t. LinDx.F / LinDx.f / x0 exist on the al_solve route only; the "
                                       "streaming route (al_solve_stream, linearize_once) carries lam and rho over "
                                       "its iterations on the host and saves no multipliers for them")
-        if tuple(f.shape) != tuple(F.shape[:3]):
-            raise NotImplementedError(f"MPC: a gradient w.r.t. LinDx needs f as [B,T-1,nx]={tuple(F.shape[:3])} "
-                                      f"(no broadcast over the batch), got {tuple(f.shape)}")
-        return F, f, x0
+        return F, f, x0   # (each in one of _as_lindx's forms: _ALSolve.backward reduces the shared ones' gradients)
 
     def _h_input(self):
         """(ineqh,) as an input of the autograd node when it asks for a gradient (_ALSolve), else ()."""
@@ -991,7 +1027,7 @@ class MPC(Module):
             raise NotImplementedError("Obstacle_MPC with linearize_once: the reference's frozen-linearisation "
                                       "module knows no obstacle rows (AL_mpc_custom.py:68, 75, 83)")
 
-        F = c = None
+        F = c = shdyn = None
         if linearize_once:
             # frozen linearisation captured once per call (al_utils_lin.py:140-169)
             # note the offset: x_{t+1} of the WARM START minus F_t z_t, not f(z_t) - F_t z_t (:154)
@@ -1000,8 +1036,11 @@ class MPC(Module):
         elif st.lin is not None:
             F = st.lin[0].detach().to(device=dev, dtype=dt).contiguous()
             c = st.lin[1].detach().to(device=dev, dtype=dt).contiguous()
+            if F.dim() < 4 or c.dim() < 3:   # shared by the batch: the data as given, with its strides
+                shdyn = (*st.lin[2], *st.lin[3])
         L = _Launcher(be, st, dims, Qd, q, self._bounds(B, dt, dev), F, c, linearize_once, self._xbounds(B, dt, dev),
-                      self._poly(B, dt, dev))
+                      self._poly(B, dt, dev), shdyn)
+        F = L.F   # (materialised by the launcher where no kernel reads the shared form)
         # the quad kernels take the obstacle / state-estimator rows too, so their factor can stay in the records
         # (dense cost, state bounds, general rows: team kernel, packed factor)
         use_qws = (need_grad and L.has_backward_ws and B >= L.quad_min_batch and not L.dense and L.xbnd is None
@@ -1061,6 +1100,8 @@ class MPC(Module):
                 import warnings
                 warnings.warn(msg, RuntimeWarning, stacklevel=3)
         if need_grad and F_last is not None:
+            if F_last.dim() < 4:   # the backward kernels read a per-instance F: materialised only here, for them
+                F_last = F_last.expand(B, T - 1, nx, n).contiguous()
             if L.nlws is not None:
                 return "workspace", L.nlws, F_last, rho_last
             if use_qws:

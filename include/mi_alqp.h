@@ -163,6 +163,32 @@ int alqp_solve_lin_f64(const AlqpDims *dims, const AlqpParams *prm, const void *
                        void *stream);
 
 /*
+ * The same solve on BATCH-SHARED DYNAMICS: F and c are addressed with an instance stride and a stage stride (words), the
+ * convention of sb_u / st_u, so that one model serves the whole batch without B copies of it:
+ *   F [nx][n]          one F for every instance and stage (LTI)    sb_F = 0,             st_F = 0
+ *   F [T-1][nx][n]     one sequence F_t for every instance (LTV)   sb_F = 0,             st_F = nx n
+ *   F [B][T-1][nx][n]  per instance, as alqp_solve_lin_* reads it  sb_F = (T-1) nx n,    st_F = nx n
+ * and c likewise without the [n] (0, 0 / 0, nx / (T-1) nx, nx), independently of F. Any other stride pair, a negative
+ * stride or a null F or c is ALQP_E_BADARG; F and c must hold (B-1) sb + (T-2) st + nx n (nx) words. Everything else -
+ * arguments, AlqpParams.variant 0 / 1 / 2 and alqp_pick_variant's rule, workspace, every flag, skip_flag, trace,
+ * factor_out, what is refused - is alqp_solve_lin_*'s, and so is every number: the kernels (k_solve_lin_shdyn,
+ * k_solve_lin_quad_shdyn) do the plain kernels' arithmetic in the same order, the result equals bit for bit that of
+ * alqp_solve_lin_* on the expanded arrays. alqp_backward_* keeps reading a per-instance F.
+ */
+int alqp_solve_lin_shared_f32(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                              const void *F, const void *c, long sb_F, long st_F, long sb_c, long st_c,
+                              const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u, void *z,
+                              void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
+                              void *factor_out, const AlqpTrace *trace, void *workspace, size_t ws_bytes,
+                              void *stream);
+int alqp_solve_lin_shared_f64(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                              const void *F, const void *c, long sb_F, long st_F, long sb_c, long st_c,
+                              const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u, void *z,
+                              void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
+                              void *factor_out, const AlqpTrace *trace, void *workspace, size_t ws_bytes,
+                              void *stream);
+
+/*
  * The same solve with a DENSE stage cost 1/2 z_t' C_t z_t + q_t' z_t: C [B][T][n][n] row-major takes the place of Qd.
  * C_t must be symmetric (the caller symmetrises; the kernel reads whole rows) and H_tt = C_t + penalty terms positive
  * definite. The reference sketches this case (al_utils.compute_cost's diag_cost=False branch) but cannot run it.
