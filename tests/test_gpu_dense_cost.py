@@ -28,9 +28,11 @@ PHI_EPS = {"f64": 1e-10, "f32": 3e-5}      # its resolution of a merit, relative
 G_FLOOR = {"f64": 1e-5, "f32": 1e-3}
 INIT_MERIT, DUAL_UPDATE, SAVE_FACTOR = 1, 2, 4
 # (nx, nu, T, B, bounds per (b, t)): four teams per wavefront + a ragged second wavefront + one dynamics stage; one
-# instance; two teams per wavefront, ragged; n = 17 (odd row length, whole-wavefront team); the largest n; strided bounds
+# instance; two teams per wavefront, ragged; n = 17 (odd row length, whole-wavefront team); the largest n; strided bounds;
+# the sizes at which Cfg's padding vanishes: n = 8 and n = 16 (pad4(N) == N, no padding column behind a row), and nx = 4
+# (pad4(NX) == NX) with odd n = 5 and NROWS = 15, one lane short of the 16-lane team
 SHAPES = [(2, 1, 2, 5, False), (2, 1, 5, 1, False), (8, 2, 4, 3, False), (13, 4, 3, 2, False), (14, 4, 3, 2, False),
-          (13, 4, 3, 2, True)]
+          (13, 4, 3, 2, True), (6, 2, 3, 5, False), (12, 4, 3, 3, False), (4, 1, 3, 9, False)]
 
 
 class _GuardedU8:

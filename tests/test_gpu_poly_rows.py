@@ -22,9 +22,12 @@ INIT_MERIT, DUAL_UPDATE, SAVE_FACTOR = 1, 2, 4
 # (nx, nu, T, B, m, layout of G and h): four teams per wavefront, the second wavefront ragged (a padding team with b
 # clamped); m above the team width 8 (two trips of the residual loop), one instance, every stride in use; m no multiple of
 # 4 (the hand-over region's padding), stage strides alone, a unit row exactly on its boundary; whole-wavefront teams;
-# the largest n; the workload's horizon, T m = 140: two trips and a tail of the strided loops
+# the largest n; the workload's horizon, T m = 140: two trips and a tail of the strided loops; the sizes at which Cfg's
+# padding vanishes: n = 8 and n = 16 (pad4(N) == N, no padding column behind a row of G), and nx = 4 (pad4(NX) == NX) with
+# odd n = 5 and NROWS = 15, one lane short of the 16-lane team
 SHAPES = [(2, 1, 2, 5, 1, "shared"), (2, 1, 5, 1, 9, "per_instance"), (8, 2, 4, 3, 5, "per_stage"), (13, 4, 3, 2, 3, "per_instance"),
-          (14, 4, 3, 2, 2, "shared"), (13, 4, 20, 2, 7, "shared")]
+          (14, 4, 3, 2, 2, "shared"), (13, 4, 20, 2, 7, "shared"), (6, 2, 3, 5, 5, "per_instance"), (12, 4, 3, 3, 5, "per_instance"),
+          (4, 1, 3, 9, 3, "shared")]
 ON_BOUND = (8, 2, 4, 3)   # the shape whose traced iterates start with a unit row exactly on its boundary
 # The iterate the traced steps start from has no row within KINK_MARGIN of its kink other than the one put there on
 # purpose (_after_one_al_iteration asserts it): on a kink the order of a dot product decides [r >= 0] and with it the
@@ -243,19 +246,24 @@ def test_full_solve_f32(nx, nu, T):
     o = ref_solve(pr, st, al_iter=2, max_newton=4, flags=INIT_MERIT | DUAL_UPDATE)
     assert (h["status"] == 1).all()
     ok = _smoke_rule(pr, h, o, f"({nx},{nu}) T={T} B=64 m={m}")
-    # lam (general rows included), rho and rn2 of the instances that took the reference's steps. A row's residual moves by
-    # at most cF times the error dz of z, cF = the largest absolute row sum over the dynamics rows (1 + |F|) and the
+    _lam_rn2_rule(pr, h, o, ok, f"({nx},{nu})")
+
+
+def _lam_rn2_rule(pr, h, o, ok, label):
+    """lam (general rows included), rho and rn2 of the instances `ok` that took the reference's steps (_smoke_rule's mask)."""
+    # A row's residual moves by at most cF times the error dz of z, cF = the largest absolute row sum over the dynamics rows (1 + |F|) and the
     # general rows (|G|); lam = max(0, lam + rho r) is built with rho = 1 and 10, and rn2 = sum of M squares r^2:
     # |dlam| <= 11 cF dz, |drn2| <= 2 sqrt(M rn2) cF dz + M (cF dz)^2; dz is the instance's own error of z (not below the
     # 1e-5 the rule asks of the median), with a factor 2 for the first iteration's iterate
+    B = pr["dims"][0]
     assert torch.equal(h["rho"], o["rho"])
-    dz = 2 * np.maximum((h["z"] - o["z"]).abs().reshape(64, -1).max(1)[0].numpy(), 1e-5)
+    dz = 2 * np.maximum((h["z"] - o["z"]).abs().reshape(B, -1).max(1)[0].numpy(), 1e-5)
     cF = max(1 + float(pr["F"].abs().sum(-1).max()), float(pr["G"].abs().sum(-1).max()))
     M = h["lam"].shape[1]
-    el = (h["lam"] - o["lam"]).abs().reshape(64, -1).max(1)[0].numpy()
+    el = (h["lam"] - o["lam"]).abs().reshape(B, -1).max(1)[0].numpy()
     er = (h["rn2"] - o["rn2"]).abs().numpy()
     rn = o["rn2"].numpy().astype(np.float64)
-    print(f"POLY full f32 ({nx},{nu}): |lam - ref| median {np.median(el):.2e} max {el[ok].max():.2e}, worst share of its bound "
+    print(f"POLY full f32 {label}: |lam - ref| median {np.median(el):.2e} max {el[ok].max():.2e}, worst share of its bound "
           f"{(el / (11 * cF * dz))[ok].max():.2f}; rn2 {(er / (2 * np.sqrt(M * rn) * cF * dz + M * (cF * dz) ** 2))[ok].max():.2f}")
     assert (el <= 11 * cF * dz)[ok].all()
     assert (er <= 2 * np.sqrt(M * rn) * cF * dz + M * (cF * dz) ** 2)[ok].all()

@@ -21,9 +21,11 @@ INIT_MERIT, DUAL_UPDATE, SAVE_FACTOR = 1, 2, 4
 # (nx, nu, T, B, state bounds per (b, t)): four teams per wavefront, the second wavefront ragged (a padding team with b
 # clamped), T*NX = 4 below the team width 8; one instance, strided bounds; two teams per wavefront, ragged, T*NX = 32 =
 # the team width; whole-wavefront teams with strided bounds, T*NX = 39 below 64; the largest n; the workload's horizon,
-# T*NX = 260: four trips and a tail of the strided loops
+# T*NX = 260: four trips and a tail of the strided loops; the sizes at which Cfg's padding vanishes: n = 8 and n = 16
+# (pad4(N) == N, no padding column behind a row; the second with strided bounds), and nx = 4 (pad4(NX) == NX) with odd
+# n = 5 and NROWS = 15, one lane short of the 16-lane team
 SHAPES = [(2, 1, 2, 5, False), (2, 1, 5, 1, True), (8, 2, 4, 3, False), (13, 4, 3, 2, True), (14, 4, 3, 2, False),
-          (13, 4, 20, 2, False)]
+          (13, 4, 20, 2, False), (6, 2, 3, 5, False), (12, 4, 3, 3, True), (4, 1, 3, 9, False)]
 ON_BOUND = (8, 2, 4, 3)   # the shape whose first traced iterate has a state exactly on its upper bound
 
 
@@ -229,18 +231,23 @@ def test_full_solve_f32(nx, nu, T):
     o = ref_solve(pr, st, al_iter=2, max_newton=4, flags=INIT_MERIT | DUAL_UPDATE)
     assert (h["status"] == 1).all()
     ok = _smoke_rule(pr, h, o, f"({nx},{nu}) T={T} B=64")
-    # lam (state rows included), rho and rn2 of the instances that took the reference's steps. A row's residual moves by
-    # at most cF = 1 + max row sum |F| times the error dz of z, lam = max(0, lam + rho r) is built with rho = 1 and 10, and
+    _lam_rn2_rule(pr, h, o, ok, f"({nx},{nu})")
+
+
+def _lam_rn2_rule(pr, h, o, ok, label):
+    """lam (state rows included), rho and rn2 of the instances `ok` that took the reference's steps (_smoke_rule's mask)."""
+    # A row's residual moves by at most cF = 1 + max row sum |F| times the error dz of z, lam = max(0, lam + rho r) is built with rho = 1 and 10, and
     # rn2 = sum of M squares r^2: |dlam| <= 11 cF dz, |drn2| <= 2 sqrt(M rn2) cF dz + M (cF dz)^2; dz is the instance's own
     # error of z (not below the 1e-5 the rule asks of the median), with a factor 2 for the first iteration's iterate
+    B = pr["dims"][0]
     assert torch.equal(h["rho"], o["rho"])
-    dz = 2 * np.maximum((h["z"] - o["z"]).abs().reshape(64, -1).max(1)[0].numpy(), 1e-5)
+    dz = 2 * np.maximum((h["z"] - o["z"]).abs().reshape(B, -1).max(1)[0].numpy(), 1e-5)
     cF = 1 + float(pr["F"].abs().sum(-1).max())
     M = h["lam"].shape[1]
-    el = (h["lam"] - o["lam"]).abs().reshape(64, -1).max(1)[0].numpy()
+    el = (h["lam"] - o["lam"]).abs().reshape(B, -1).max(1)[0].numpy()
     er = (h["rn2"] - o["rn2"]).abs().numpy()
     rn = o["rn2"].numpy().astype(np.float64)
-    print(f"XBOX full f32 ({nx},{nu}): |lam - ref| median {np.median(el):.2e} max {el[ok].max():.2e}, worst share of its bound "
+    print(f"XBOX full f32 {label}: |lam - ref| median {np.median(el):.2e} max {el[ok].max():.2e}, worst share of its bound "
           f"{(el / (11 * cF * dz))[ok].max():.2f}; rn2 {(er / (2 * np.sqrt(M * rn) * cF * dz + M * (cF * dz) ** 2))[ok].max():.2f}")
     assert (el <= 11 * cF * dz)[ok].all()
     assert (er <= 2 * np.sqrt(M * rn) * cF * dz + M * (cF * dz) ** 2)[ok].all()
