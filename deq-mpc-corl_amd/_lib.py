@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_ALQP_LIB") or os.path.join(_HERE, "csrc", "libmi_alqp.so")   # MI_ALQP_LIB: A/B experiments with a second build of the same ABI
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class AlqpDims(C.Structure):
@@ -94,6 +94,10 @@ _SIGS = {
     "alqp_solve_lin_poly": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), _P, _P, _P, _P, _P, _P, _P,
                                       C.c_long, C.c_long, _P, _P, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
                                       _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(AlqpTrace), _P]),
+    "alqp_solve_lin_gen": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), _P, _P, _P, _P, _P, _P, _P,
+                                     C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
+                                     C.POINTER(AlqpTrace), _P, C.c_size_t, _P,
+                                     _P, _P, _P, C.c_long, C.c_long, _P, _P, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long]),
     "alqp_newton_step": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                    C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "alqp_merit": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,

@@ -358,6 +358,63 @@ class HipBackend:
         _lib.check(rc, "alqp_solve_lin_poly_" + sfx)
         return True
 
+    def solve_lin_gen(self, dims, Qd_or_C, q, F, c, x0, ulo, uhi, sb_u, st_u, xbnd, poly, z, lam, rho, phi,
+                      rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
+                      n_ls=20, flags=_lib.ALQP_INIT_MERIT | _lib.ALQP_DUAL_UPDATE, rho_scale=10.0,
+                      trace=None, variant=None, skip=None, newton_counts=None, exit_tol=1e-3):
+        """solve_lin with two or three of a dense cost, state bounds and general rows together (alqp_solve_lin_gen).
+        Qd_or_C: C [B,T,n,n] (a dense cost) or Qd [B,T,n]; xbnd: (xlo, xhi, sb_x, st_x) as solve_lin_xbox takes them,
+        or None; poly: (G, h, m, sb_g, st_g, sb_h, st_h) as solve_lin_poly takes them, or None. lam is
+        [B, T nx + T (2 nu + [2 nx] + [m])]: per stage [u - uhi | -u + ulo | x - xhi | -x + xlo | G_t z_t - h_t] behind the
+        equality rows. Team kernel only (variant None / "auto" / "team"), no workspace; everything else as solve_lin."""
+        B, T, nx, nu = dims
+        n = nx + nu
+        dt = z.dtype
+        sfx = _dt(z)
+        dense = Qd_or_C is not None and Qd_or_C.dim() == 4
+        if dense and tuple(Qd_or_C.shape) != (B, T, n, n):
+            raise ValueError(f"mi_alqp: C has shape {tuple(Qd_or_C.shape)}, expected {(B, T, n, n)}")
+        xlo, xhi, sb_x, st_x = xbnd if xbnd is not None else (None, None, 0, 0)
+        G, h, m, sb_g, st_g, sb_h, st_h = poly if poly is not None else (None, None, 0, 0, 0, 0, 0)
+        M = T * nx + T * (2 * nu + (2 * nx if xbnd is not None else 0) + (max(int(m), 0) if poly is not None else 0))
+        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
+            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, these rows need [B, {M}]")
+        if xbnd is not None:
+            for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
+                if t is None:
+                    raise ValueError(f"mi_alqp: {name} is required")
+                if t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
+                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
+        if poly is not None:
+            for t, name, sb, st, w in ((G, "ineqG", sb_g, st_g, m * n), (h, "ineqh", sb_h, st_h, m)):
+                if t is not None and m >= 1 and t.numel() < (B - 1) * sb + (T - 1) * st + w:
+                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
+        d = _lib.AlqpDims(B, T, nx, nu)
+        vnum = {"auto": 0, "team": 1, "quad": 2}[variant or "auto"]   # quad goes through: the library refuses it
+        self.last_variant = "team"
+        skp = _ptr(skip, "skip", torch.float64, True)
+        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags, rho_scale, vnum, skp.value if skp is not None else None)
+        if newton_counts is not None:
+            self._exit_in_kernel(p, B, z.device, newton_counts, exit_tol)
+        tr = None
+        if trace is not None:
+            tr = _lib.AlqpTrace(*[
+                (trace[k].data_ptr() if trace.get(k) is not None else None)
+                for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
+        fn = getattr(self.lib, "alqp_solve_lin_gen_" + sfx)
+        rc = fn(C.byref(d), C.byref(p), None if dense else _ptr(Qd_or_C, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
+                _ptr(c, "c", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
+                sb_u, st_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+                _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
+                _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
+                _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None, None, 0, _stream(),
+                _ptr(Qd_or_C, "C", dt) if dense else None, _ptr(xlo, "x_lower", dt, True), _ptr(xhi, "x_upper", dt, True),
+                sb_x, st_x, _ptr(G, "ineqG", dt, True), _ptr(h, "ineqh", dt, True), m, sb_g, st_g, sb_h, st_h)
+        if rc == _lib.ALQP_E_COOP and newton_counts is not None:
+            return False
+        _lib.check(rc, "alqp_solve_lin_gen_" + sfx)
+        return True
+
     def _exit_in_kernel(self, p, B, device, newton_counts, exit_tol):
         """AlqpParams fields of ALQP_EXIT_IN_KERNEL: the cached scratch (arrival counter + 2 x B partial sums)."""
         scr = self._scratch(("exit", device), 2 * B + 2, torch.float64, device)

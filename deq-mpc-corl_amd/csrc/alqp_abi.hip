@@ -257,6 +257,58 @@ int solve_lin_poly_impl(const AlqpDims *dims, const AlqpParams *prm, const void 
     return dispatch_solve_poly<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
 }
 
+// Two or three of dense cost, state bounds and general rows together: the non-null set picks the object (build.sh,
+// alqp_team_gen_*). Team kernel only, like each of them alone.
+template <typename real>
+int solve_lin_gen_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
+                       const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                       void *z, void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
+                       void *factor_out, const AlqpTrace *trace, void *stream, const void *Cm, const void *x_lo,
+                       const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m, long sb_g,
+                       long st_g, long sb_h, long st_h) {
+    if (!dims_ok(dims) || !prm || !q || !F || !c || !x0 || !u_lo || !u_hi || !z || !lam || !rho || !phi)
+        return ALQP_E_BADARG;
+    if (!x_lo != !x_hi || !G != !h) return ALQP_E_BADARG;
+    const int mask = (Cm ? kGenDense : 0) | (x_lo ? kGenXbox : 0) | (G ? kGenPoly : 0);
+    if (mask != 3 && mask != 5 && mask != 6 && mask != 7) return ALQP_E_BADARG;   // fewer than two features
+    if (!Cm && !Qd) return ALQP_E_BADARG;
+    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
+    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
+    if (x_lo && (sb_x < 0 || st_x < 0)) return ALQP_E_BADARG;
+    if (G && (m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0)) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
+    // the horizon must fit the LDS: the team image, plus the hand-over region of 2 pad4(m) words per team with rows
+    const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
+    if (img == 0) return ALQP_E_UNSUPPORTED;
+    const size_t lds = img + (G ? (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real) : 0);
+    if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    GenSolveArgs<real> a = {};
+    if (!set_solve<real>(dims, prm, Cm ? nullptr : Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info,
+                         status, a))
+        return ALQP_E_BADARG;
+    a.C = (const real *)Cm;
+    if (x_lo) { a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x; }
+    if (G) {
+        a.G = (const real *)G; a.h = (const real *)h; a.m = m;
+        a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
+    }
+    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
+    TraceArgs<real> tr = {};
+    if (trace) {
+        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
+        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
+    }
+    const TraceArgs<real> *trp = trace ? &tr : nullptr;
+    const hipStream_t s = (hipStream_t)stream;
+    switch (mask) {
+        case kGenDense | kGenXbox: return dispatch_solve_gen<real, kGenDense | kGenXbox>(dims->nx, dims->nu, a, trp, s);
+        case kGenDense | kGenPoly: return dispatch_solve_gen<real, kGenDense | kGenPoly>(dims->nx, dims->nu, a, trp, s);
+        case kGenXbox | kGenPoly: return dispatch_solve_gen<real, kGenXbox | kGenPoly>(dims->nx, dims->nu, a, trp, s);
+        default: return dispatch_solve_gen<real, kGenDense | kGenXbox | kGenPoly>(dims->nx, dims->nu, a, trp, s);
+    }
+}
+
 // nonlinear fused solve: workspace = [records | F linearisations [B][T-1][nx][n]]
 template <typename real>
 size_t nonlin_ws_bytes(int nx, int nu, int B, int T) {
@@ -354,7 +406,7 @@ int backward_impl(const AlqpDims *dims, const void *factor, void *workspace, siz
 // ---- C ABI -------------------------------------------------------------------------------
 extern "C" {
 
-int alqp_abi_version(void) { return 16; }
+int alqp_abi_version(void) { return 17; }
 
 size_t alqp_workspace_bytes_nonlin(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;
@@ -472,6 +524,21 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
         return alqp::solve_lin_poly_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u,    \
                                                G, h, m, sb_g, st_g, sb_h, st_h, z, lam, rho, phi,     \
                                                rnorm2, info, status, factor_out, trace, stream);      \
+    }                                                                                                 \
+    int alqp_solve_lin_gen_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,         \
+                                 const void *q, const void *F, const void *c, const void *x0,         \
+                                 const void *u_lo, const void *u_hi, long sb_u, long st_u, void *z,   \
+                                 void *lam, void *rho, void *phi, void *rnorm2, int *info,            \
+                                 unsigned char *status, void *factor_out, const AlqpTrace *trace,     \
+                                 void *workspace, size_t ws_bytes, void *stream, const void *C,       \
+                                 const void *x_lo, const void *x_hi, long sb_x, long st_x,            \
+                                 const void *G, const void *h, int m, long sb_g, long st_g,           \
+                                 long sb_h, long st_h) {                                              \
+        (void)workspace; (void)ws_bytes;                                                              \
+        return alqp::solve_lin_gen_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z,  \
+                                              lam, rho, phi, rnorm2, info, status, factor_out, trace, \
+                                              stream, C, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, \
+                                              sb_h, st_h);                                            \
     }                                                                                                 \
     int alqp_newton_step_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
                                const void *x0, const void *lam, const void *rho, const void *Qd,      \

@@ -51,6 +51,19 @@ struct PolySolveArgs : SolveArgs<real> {
     long sb_h, st_h;
 };
 
+// The fused solve with two or three of the above together (k_solve_lin_gen<.., DENSE, XBOX, POLY, ..>): every member of the
+// three structs above behind the plain arguments; an instantiation reads those of its flags (Qd only without DENSE).
+template <typename real>
+struct GenSolveArgs : SolveArgs<real> {
+    const real *C;
+    const real *xlo, *xhi;
+    long sb_x, st_x;
+    const real *G, *h;
+    int m;
+    long sb_g, st_g;
+    long sb_h, st_h;
+};
+
 // The fused solve on batch-shared dynamics (k_solve_lin_shdyn, k_solve_lin_quad_shdyn): F and c addressed with an
 // instance stride and a stage stride like the bounds (sb_u / st_u), again in a type of its own.
 // The stage stride of either is 0 or the packed one (nx n / nx; alqp_solve_lin_shared_* takes nothing else), so the kernels

@@ -26,6 +26,8 @@ template <typename real>
 inline int flags_of(const PolySolveArgs<real> &a) { return a.flags; }
 template <typename real>
 inline int flags_of(const ShdynSolveArgs<real> &a) { return a.flags; }
+template <typename real>
+inline int flags_of(const GenSolveArgs<real> &a) { return a.flags; }
 template <typename Fn, typename A0, typename... Rest>
 int launch_maybe_coop(Fn fn, unsigned grid, size_t lds, hipStream_t stream, A0 a0, Rest... rest) {
     if (flags_of(a0) & ALQP_EXIT_IN_KERNEL) {
@@ -75,6 +77,10 @@ template <typename real>
 int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
+// MASK: kGenDense | kGenXbox | kGenPoly, two or three of them; one object per mask (alqp_team_gen_*, -DALQP_GEN_UNIT=<mask>)
+constexpr int kGenDense = 1, kGenXbox = 2, kGenPoly = 4;
+template <typename real, int MASK>
+int dispatch_solve_gen(int nx, int nu, const GenSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 size_t lds_query(int nx, int nu, int T);   // bytes of the team LDS image, 0: no such instance
 

@@ -1,7 +1,7 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
 #if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT) || defined(ALQP_POLY_UNIT) || \
-    defined(ALQP_SHDYN_UNIT)
+    defined(ALQP_SHDYN_UNIT) || defined(ALQP_GEN_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -39,7 +39,14 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // through an instance stride and a stage stride (a.sb_F / a.mt_F, a.sb_c / a.mt_c; ALQP_F_STAGE / ALQP_C_STAGE in Team), so
 // that one F, or one sequence F_t, serves the whole batch. Same arithmetic in the same order on the same values as
 // k_solve_lin; capped and uncapped builds chosen by the plain kernel's rule (dispatch_solve_shdyn).
-#if defined(ALQP_DENSE_UNIT)
+// The combination units (-DALQP_GEN_UNIT=<mask>, mask = 1 dense | 2 state bounds | 4 general rows, one object per mask with
+// two or three bits set), a sixth header: k_solve_lin_gen, the three flags as template parameters and every feature's
+// arguments in one GenSolveArgs. Multipliers per stage [u | x | G] (Team), LDS image that of the flags it has. Uncapped
+// builds only, and no spilling instantiation (tools/spill_report.py), for the reason given above.
+#if defined(ALQP_GEN_UNIT)
+template <typename real, int NX, int NU, bool DENSE, bool XBOX, bool POLY, bool TRACE>
+__global__ __launch_bounds__(64, 1) void k_solve_lin_gen(GenSolveArgs<real> a, TraceArgs<real> tr) {
+#elif defined(ALQP_DENSE_UNIT)
 template <typename real, int NX, int NU, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_dense(DenseSolveArgs<real> a, TraceArgs<real> tr) {
     constexpr bool DENSE = true, XBOX = false, POLY = false;
@@ -69,7 +76,10 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     const int b_raw = blockIdx.x * C::QPW + team;
     const bool active = b_raw < a.B;
     const int b = active ? b_raw : a.B - 1;
-#ifdef ALQP_POLY_UNIT
+#if defined(ALQP_GEN_UNIT)
+    const int T = a.T, M = C::M(T) + (XBOX ? 2 * T * NX : 0) + (POLY ? T * a.m : 0), neq = T * NX;
+    const int team_words = C::team_words(T) + (POLY ? 2 * pad4(a.m) : 0);   // the team image, then the hand-over region
+#elif defined(ALQP_POLY_UNIT)
     const int T = a.T, M = C::M(T) + T * a.m, neq = T * NX;
     const int team_words = C::team_words(T) + 2 * pad4(a.m);   // the team image, then the hand-over region
 #else
@@ -83,7 +93,10 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.stamp(-1);
 #endif
     tm.init(smem + (size_t)team * team_words + opaque_zero(), li, team * G, T, b);
-#ifdef ALQP_DENSE_UNIT
+#if defined(ALQP_GEN_UNIT)
+    if constexpr (DENSE) tm.gC = a.C + (size_t)b * T * N * N;
+    else tm.gQd = a.Qd + (size_t)b * T * N;
+#elif defined(ALQP_DENSE_UNIT)
     tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
 #else
     tm.gQd = a.Qd + (size_t)b * T * N;
@@ -101,6 +114,19 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.gulo = a.ulo + (size_t)b * a.sb_u;
     tm.guhi = a.uhi + (size_t)b * a.sb_u;
     tm.st_u = a.st_u;
+#ifdef ALQP_GEN_UNIT
+    if constexpr (XBOX) {
+        tm.gxlo = a.xlo + (size_t)b * a.sb_x;
+        tm.gxhi = a.xhi + (size_t)b * a.sb_x;
+        tm.st_x = a.st_x;
+    }
+    if constexpr (POLY) {
+        tm.gG = a.G + (size_t)b * a.sb_g;
+        tm.gh = a.h + (size_t)b * a.sb_h;
+        tm.st_g = a.st_g; tm.st_h = a.st_h; tm.pm = a.m;
+        tm.ps = tm.Xp + pad4(T * C::XT);
+    }
+#endif
 #ifdef ALQP_XBOX_UNIT
     tm.gxlo = a.xlo + (size_t)b * a.sb_x;
     tm.gxhi = a.xhi + (size_t)b * a.sb_x;
@@ -407,7 +433,17 @@ inline long team_simds() {   // SIMDs of the device (4 per CU)
     return n;
 }
 
-#if defined(ALQP_SHDYN_UNIT)
+#if defined(ALQP_GEN_UNIT)
+template <typename real, int MASK>
+int dispatch_solve_gen(int nx, int nu, const GenSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
+    constexpr bool D = (MASK & kGenDense) != 0, X = (MASK & kGenXbox) != 0, P = (MASK & kGenPoly) != 0;
+    const int extra = P ? 2 * pad4(a.m) : 0;
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (tr) return launch_team_kernel_extra<real, NX, NU>(k_solve_lin_gen<real, NX, NU, D, X, P, true>, a.B, a.T, extra, stream, a, *tr);
+        return launch_team_kernel_extra<real, NX, NU>(k_solve_lin_gen<real, NX, NU, D, X, P, false>, a.B, a.T, extra, stream, a, TraceArgs<real>{});
+    });
+}
+#elif defined(ALQP_SHDYN_UNIT)
 template <typename real>
 int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {   // dispatch_solve's occupancy rule
@@ -483,8 +519,12 @@ size_t lds_query(int nx, int nu, int T) {
 // The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
 // So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT), the state-bound ones (-DALQP_XBOX_UNIT) and
-// the general-row ones (-DALQP_POLY_UNIT) and the shared-dynamics ones (-DALQP_SHDYN_UNIT).
-#if defined(ALQP_SHDYN_UNIT)
+// the general-row ones (-DALQP_POLY_UNIT) and the shared-dynamics ones (-DALQP_SHDYN_UNIT), and each combination of flags
+// (-DALQP_GEN_UNIT=<mask>).
+#if defined(ALQP_GEN_UNIT)
+template int dispatch_solve_gen<float, ALQP_GEN_UNIT>(int, int, const GenSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
+template int dispatch_solve_gen<double, ALQP_GEN_UNIT>(int, int, const GenSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+#elif defined(ALQP_SHDYN_UNIT)
 template int dispatch_solve_shdyn<float>(int, int, const ShdynSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_shdyn<double>(int, int, const ShdynSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 #elif defined(ALQP_POLY_UNIT)

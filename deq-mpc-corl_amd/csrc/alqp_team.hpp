@@ -213,6 +213,12 @@ __device__ inline void wave_sync() { asm volatile("" ::: "memory"); }
 // row hi of the rank-one sum in registers, like DENSE's cr[N], and adds it to row hi of Hs behind the SYRK phase. The
 // three T*NU loops below get a T*pm twin: a row's residual along the Newton direction is r0 + alpha s, two dot products
 // per row and Newton step. Every POLY statement sits behind `if constexpr`.
+// Flags together (k_solve_lin_gen only): per stage [u - uhi | -u + ulo | x - xhi | -x + xlo | G_t z_t - h_t], stage stride
+// 2 NU + XR + pm; every offset below is written with XR and (POLY ? pm : 0) in place, so the single-flag instantiations
+// keep the numbers they had. DENSE && POLY would hold three rows of N per H lane (C_t, C_{t+1} in flight, the rank-one
+// sum) next to G_{t+1}'s first trip, and the fp64 builds at (13,4) and (14,4) spill. There, and only there: row hi of C_t
+// is fetched at its own stage, the first trip of G_t in place like the later ones, and crow starts from cr so that one row
+// C_t[hi,:] + rho sum_k a_k G_k[hi] G_k goes onto Hs in one pass.
 template <typename real, int NX, int NU, bool DENSE = false, bool XBOX = false, bool POLY = false>
 struct Team {
     using C = Cfg<real, NX, NU>;
@@ -398,8 +404,9 @@ struct Team {
         if (li < NX) req[(T - 1) * NX + li] = no_init ? real(0) : zs[li] - gx0[li];
         fetch_F(0, fbuf);
         real Qn = isH ? (DENSE ? real(0) : gQd[hi]) : real(0), qn = isH ? gq[hi] : real(0);
-        real crn[DENSE ? N : 1], cr[DENSE ? N : 1];   // DENSE: row hi of C_{t+1} in flight, of C_t in use
-        if constexpr (DENSE) fetch_C(0, crn);
+        // DENSE: row hi of C_{t+1} in flight, of C_t in use. DENSE && POLY: no row in flight, see the note at the struct
+        real crn[DENSE && !POLY ? N : 1], cr[DENSE ? N : 1];
+        if constexpr (DENSE && !POLY) fetch_C(0, crn);
         real cn = isW ? (gxnext ? gxnext[wr] : gc[wr]) : real(0);
         // multipliers this lane needs at stage t (global memory, prefetched a stage ahead):
         //   x rows: lam of the eq row that pins x_t (init row for t = 0, dynamics row t-1)
@@ -418,15 +425,15 @@ struct Team {
             }
         }
         // POLY: row li of G_0, its right-hand side and multiplier (the first trip of the residual loop), a stage ahead too
-        real grn[POLY ? N : 1], hpn = 0, lpn = 0;
+        real grn[POLY && !DENSE ? N : 1], hpn = 0, lpn = 0;
         real crow[POLY ? N : 1];   // POLY: row hi of rho sum_k [r_k >= 0] G_k' G_k of the stage in hand
-        if constexpr (POLY) {
+        if constexpr (POLY && !DENSE) {
             const int k = li < pm ? li : 0;
             const real *Gk = grow(0, k);
 #pragma unroll
             for (int j = 0; j < N; ++j) grn[j] = Gk[j];
             hpn = hrow(0, k);
-            lpn = lams[T * NX + 2 * NU + k];
+            lpn = lams[T * NX + 2 * NU + XR + k];
         }
         // Sb may hold s_eq of the previous Newton step: restore its constant zero rows
         for (int e = li; e < RB * NP; e += G) Sb[e] = 0;
@@ -435,7 +442,7 @@ struct Team {
             const bool dyn = t < T - 1;
             const real Qv = Qn, qv = qn, cv = cn, la = lan, lb = lbn;
             const real lxu = lxun, lxl = lxln, bxu = bxun, bxl = bxln;
-            if constexpr (DENSE) {
+            if constexpr (DENSE && !POLY) {
 #pragma unroll
                 for (int k = 0; k < N; ++k) cr[k] = crn[k];
             }
@@ -459,7 +466,10 @@ struct Team {
             wave_sync();
             // ---- prefetch the next stage's inputs (they stay in flight during this stage)
             if (t + 2 < T) fetch_F(t + 1, fbuf);
-            if constexpr (DENSE) {
+            if constexpr (DENSE && POLY) {
+                fetch_C(t, cr);   // at its own stage: in flight under the dynamics residual and the row residuals only
+                if (t + 1 < T && isH) qn = gq[(t + 1) * N + hi];
+            } else if constexpr (DENSE) {
                 if (t + 1 < T) fetch_C(t + 1, crn);
                 if (t + 1 < T && isH) qn = gq[(t + 1) * N + hi];
             } else {
@@ -497,21 +507,26 @@ struct Team {
             wave_sync();
             if constexpr (POLY) {
                 // ---- the stage's pm row residuals, once per team: weight and activity into ps for the H lanes
-                if (li < pm) poly_hand_over(t, li, grn, hpn, lpn);
-                for (int k = li + G; k < pm; k += G) {   // pm above the team width: further trips, fetched in place
+                if constexpr (!DENSE) {
+                    if (li < pm) poly_hand_over(t, li, grn, hpn, lpn);
+                }
+                // pm above the team width: further trips, fetched in place (DENSE: the first trip too)
+                for (int k = DENSE ? li : li + G; k < pm; k += G) {
                     const real *Gk = grow(t, k);
                     real gr[N];
 #pragma unroll
                     for (int j = 0; j < N; ++j) gr[j] = Gk[j];
-                    poly_hand_over(t, k, gr, hrow(t, k), lams[T * NX + t * (2 * NU + pm) + 2 * NU + k]);
+                    poly_hand_over(t, k, gr, hrow(t, k), lams[T * NX + t * (2 * NU + XR + pm) + 2 * NU + XR + k]);
                 }
-                if (t + 1 < T) {   // the next stage's first trip: in flight during this stage
-                    const int k = li < pm ? li : 0;
-                    const real *Gk = grow(t + 1, k);
+                if constexpr (!DENSE) {
+                    if (t + 1 < T) {   // the next stage's first trip: in flight during this stage
+                        const int k = li < pm ? li : 0;
+                        const real *Gk = grow(t + 1, k);
 #pragma unroll
-                    for (int j = 0; j < N; ++j) grn[j] = Gk[j];
-                    hpn = hrow(t + 1, k);
-                    lpn = lams[T * NX + (t + 1) * (2 * NU + pm) + 2 * NU + k];
+                        for (int j = 0; j < N; ++j) grn[j] = Gk[j];
+                        hpn = hrow(t + 1, k);
+                        lpn = lams[T * NX + (t + 1) * (2 * NU + XR + pm) + 2 * NU + XR + k];
+                    }
                 }
                 wave_sync();
             }
@@ -589,8 +604,13 @@ struct Team {
                     // g_t[hi] += sum_k w_k G_k[hi]; crow = row hi of sum_k a_k G_k' G_k (w_k, a_k from ps; G_t from L2,
                     // every H lane of the team reads the same row)
                     const int mp = pad4(pm);
+                    if constexpr (DENSE) {   // one accumulator row: C_t[hi,:] + the rank-one sum, onto Hs in one pass below
 #pragma unroll
-                    for (int j = 0; j < N; ++j) crow[j] = 0;
+                        for (int j = 0; j < N; ++j) crow[j] = cr[j];
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < N; ++j) crow[j] = 0;
+                    }
                     for (int k = 0; k < pm; ++k) {
                         const real *Gk = grow(t, k);
                         real gk[N];
@@ -645,7 +665,7 @@ struct Team {
             TSTAMP(1);
             // ---- diagonal of H_tt on top of the SYRK result (same lane order: in-order LDS)
             if (isH) Hs[hi * HP + hi] += D;
-            if constexpr (DENSE) {
+            if constexpr (DENSE && !POLY) {
                 // row hi of C_t on top of row hi of H_tt (the panel reads the lower triangle; C_t is symmetric)
                 if (isH) {
 #pragma unroll
@@ -962,7 +982,7 @@ struct Team {
                     r0 = fma_(gv, zs[t * N + j], r0);
                     sd = fma_(gv, at_z ? real(0) : ds[t * N + j], sd);
                 }
-                const real lk = lams[neq + t * (2 * NU + pm) + 2 * NU + k];
+                const real lk = lams[neq + t * (2 * NU + XR + pm) + 2 * NU + XR + k];
                 real alpha = 1;
 #pragma unroll
                 for (int kc = 0; kc < K; ++kc) {
@@ -1049,7 +1069,7 @@ struct Team {
                 real r = -hrow(t, k);
 #pragma unroll
                 for (int j = 0; j < N; ++j) r = fma_(Gk[j], zs[t * N + j], r);
-                const int row = neq + t * (2 * NU + pm) + 2 * NU + k;
+                const int row = neq + t * (2 * NU + XR + pm) + 2 * NU + XR + k;
                 const real a = fma_(rho, r, lams[row]);
                 lams[row] = a < 0 ? real(0) : a;
             }

@@ -52,6 +52,16 @@ N_LS = 20        # al_utils.py:619
 RHO_SCALE = 10.0  # AL_mpc.py:325
 SE_NO_BOUND = 1e20  # state estimator: |u| bound that is never active (rho_max * SE_NO_BOUND is finite in fp32)
 
+# Two of diag_cost=False, x_lower / x_upper and ineqG / ineqh together need a backend with `solve_lin_gen` (the fused team
+# kernel's combined instances); without it these are raised, in MPC.__init__ for a backend given
+# there and in the guard block of the solve for the lazily resolved default
+_NO_DENSE_XBOX = ("MPC: x_lower / x_upper with diag_cost=False: no kernel instance takes "
+                  "both the dense cost and the state-bound rows")
+_NO_DENSE_POLY = ("MPC: ineqG / ineqh with diag_cost=False: no kernel instance takes both the "
+                  "dense cost and the general rows")
+_NO_XBOX_POLY = ("MPC: ineqG / ineqh with x_lower / x_upper: no kernel instance takes both; write "
+                 "the state box as rows of ineqG (G = [I 0; -I 0], h = [x_upper; -x_lower])")
+
 
 def _detach_maybe(t):
     if t is None:
@@ -77,6 +87,7 @@ class _Launcher:
         self.dense = Qd.dim() == 4             # Qd is all of C [B,T,n,n] (MPC(diag_cost=False)): solve_lin_dense, team kernel
         self.xbnd = xbnd                       # (xlo, xhi, sb_x, st_x) of MPC(x_lower=, x_upper=): solve_lin_xbox, team kernel
         self.poly = poly                       # (G, h, m, sb_g, st_g, sb_h, st_h) of MPC(ineqG=, ineqh=): solve_lin_poly, team kernel
+        self.gen = self.dense + (xbnd is not None) + (poly is not None) >= 2   # two or three of them: solve_lin_gen, team kernel
         self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
         self.has_backward_ws = hasattr(be, "backward_ws")
         self.has_solve_nonlin = hasattr(be, "solve_nonlin")
@@ -112,6 +123,10 @@ class _Launcher:
 
     def lin(self, info=True, **kw):
         st = self.st
+        if self.gen:
+            return self.be.solve_lin_gen(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, self.xbnd, self.poly,
+                                         st.z, st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
+                                         **self._out, **kw)
         if self.xbnd is not None:
             return self.be.solve_lin_xbox(self.dims, self.Qd, self.q, self.F, self.c, *self._x0_bounds, *self.xbnd, st.z,
                                           st.lam, st.rho, self.phi, info=self.info if info else None, n_ls=N_LS,
@@ -195,6 +210,9 @@ class _ALSolve(torch.autograd.Function):
     ``ineqh`` requires grad it is one more input, behind ``dyn``: the rows enter g as G_k' (lam_k + rho max(G_k z - h_k, 0)),
     so with the active set and the multipliers held fixed dh[b,t,k] = -rho_last [G_k z_final,t - h_k >= 0] (G_k . w_t),
     formed here in PyTorch from w = q_grad and reduced over the axes ``ineqh`` broadcast over.
+
+    The three together: the paragraphs above compose - one saved factor holds whatever went onto
+    H_tt, and each gradient is formed from the same w as for its feature alone.
     """
 
     @staticmethod
@@ -301,17 +319,22 @@ class MPC(Module):
     entry means "no bound". The reference carries the two arguments but never built their rows (al_utils.py:294-302
     are commented out). ``lamda_prev`` is then [B, T nx + T (2 nu + 2 nx)]: the equality rows, then per stage
     [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower]. LinDx routes only (the fused team kernel, at any
-    batch): not with a callable ``dx``, ``linearize_once``, ``state_estimator``, ``Obstacle_MPC`` or ``diag_cost=False``.
+    batch): not with a callable ``dx``, ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``.
     All gradients above stay available, taken with the active set held fixed.
 
     ``ineqG`` / ``ineqh`` (both or neither): m >= 1 general linear rows G_t tau_t <= h_t per stage, on all
     T stages next to the control bounds. ``ineqG`` is [m,n], [T,m,n] or [B,T,m,n], ``ineqh`` [m], [T,m] or [B,T,m]
     (independently); a non-finite ``ineqh`` entry means "no row". The reference carries the two arguments, but the code
     that reads them is never called (AL_mpc.py:496-498). ``lamda_prev`` is then [B, T nx + T (2 nu + m)]: the equality
-    rows, then per stage [u - u_upper | -u + u_lower | G_t tau_t - h_t]. LinDx routes only, like the state bounds, and not
-    together with them (a state box is 2 nx rows of G). The gradients above stay available, and the solve is also
-    differentiable w.r.t. ``ineqh`` (active set held fixed); an ``ineqG`` that requires grad raises
-    ``NotImplementedError``.
+    rows, then per stage [u - u_upper | -u + u_lower | G_t tau_t - h_t]. LinDx routes only, like the state bounds. The
+    gradients above stay available, and the solve is also differentiable w.r.t. ``ineqh`` (active set held fixed); an
+    ``ineqG`` that requires grad raises ``NotImplementedError``.
+
+    ``diag_cost=False``, ``x_lower`` / ``x_upper`` and ``ineqG`` / ``ineqh`` go together, any two or all three (DESIGN
+    section 23; ``HipBackend.solve_lin_gen``, the fused team kernel at any batch). ``lamda_prev`` is then
+    [B, T nx + T (2 nu + [2 nx] + [m])]: the equality rows, then per stage
+    [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower | G_t tau_t - h_t]. Routes, guards and gradients are those
+    of each feature alone. A backend without ``solve_lin_gen`` raises ``NotImplementedError`` for a combination.
     """
 
     def __init__(self, n_state, n_ctrl, T, u_lower=None, u_upper=None, u_init=None, x_init=None,
@@ -334,27 +357,27 @@ class MPC(Module):
             raise ValueError("exit_mode must be 'reference' or 'fixed'")
         if (x_lower is None) != (x_upper is None):
             raise ValueError("MPC: x_lower and x_upper go together (pass +-inf for a side without a bound)")
+        # combinations of the dense cost, the state bounds and the general rows run on solve_lin_gen; a backend given here
+        # is asked now, the default one (resolved lazily) in the guard block of the solve
+        no_gen = backend is not None and not hasattr(backend, "solve_lin_gen")
         if x_lower is not None:
             # the state-bound rows live in the fused team kernel of the LinDx routes alone (alqp_solve_lin_xbox)
             if state_estimator:
                 raise NotImplementedError("MPC: x_lower / x_upper with state_estimator: that variant runs on the "
                                           "nonlinear-caller kernels, which know no state-bound rows")
-            if not diag_cost:
-                raise NotImplementedError("MPC: x_lower / x_upper with diag_cost=False: no kernel instance takes "
-                                          "both the dense cost and the state-bound rows")
+            if not diag_cost and no_gen:
+                raise NotImplementedError(_NO_DENSE_XBOX)
         if ineqG is not None or ineqh is not None:
             # the general rows live in the fused team kernel of the LinDx routes alone (alqp_solve_lin_poly)
-            if not diag_cost:   # (before anything is asked of ineqG's shape or of ineqh)
-                raise NotImplementedError("MPC: ineqG / ineqh with diag_cost=False: no kernel instance takes both the "
-                                          "dense cost and the general rows")
+            if not diag_cost and no_gen:   # (before anything is asked of ineqG's shape or of ineqh)
+                raise NotImplementedError(_NO_DENSE_POLY)
             if ineqG is None or ineqh is None:
                 raise ValueError("MPC: ineqG and ineqh go together")
             if state_estimator:
                 raise NotImplementedError("MPC: ineqG / ineqh with state_estimator: that variant runs on the "
                                           "nonlinear-caller kernels, which know no general rows")
-            if x_lower is not None:
-                raise NotImplementedError("MPC: ineqG / ineqh with x_lower / x_upper: no kernel instance takes both; write "
-                                          "the state box as rows of ineqG (G = [I 0; -I 0], h = [x_upper; -x_lower])")
+            if x_lower is not None and no_gen:
+                raise NotImplementedError(_NO_XBOX_POLY)
             ineqG, ineqh = torch.as_tensor(ineqG), torch.as_tensor(ineqh)
             if ineqG.requires_grad:
                 raise NotImplementedError("MPC: a gradient w.r.t. ineqG is not built (it needs the multiplier estimate of "
@@ -962,6 +985,14 @@ class MPC(Module):
         if not be.supported(B, T, nx, nu, dt):
             raise RuntimeError(f"mi_alqp: no kernel instance for (nx={nx}, nu={nu}, T={T}, {dt}); "
                                "add it to ALQP_FOR_EACH_DIMS in csrc/alqp_dims.hpp")
+        if not hasattr(be, "solve_lin_gen"):
+            # (a backend given to the constructor was refused there; this is the lazily resolved default's turn)
+            if self.x_lower is not None and not self.diag_cost:
+                raise NotImplementedError(_NO_DENSE_XBOX)
+            if self.ineqG is not None and not self.diag_cost:
+                raise NotImplementedError(_NO_DENSE_POLY)
+            if self.ineqG is not None and self.x_lower is not None:
+                raise NotImplementedError(_NO_XBOX_POLY)
         if not self.diag_cost:
             # the dense cost lives in the fused team kernel alone (alqp_solve_lin_dense): everything that reaches the
             # nonlinear-caller kernels or a compiled-in model reads diag(C)
@@ -988,7 +1019,7 @@ class MPC(Module):
                                           "nonlinear-caller kernels and the compiled-in models know no state-bound rows")
             if st.lam.shape[1] != self.neq + self.nineq:
                 raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the state bounds need "
-                                 f"{self.neq + self.nineq} = T nx + T (2 nu + 2 nx)")
+                                 f"{self.neq + self.nineq} = T nx + T (2 nu + 2 nx{' + m' if self.n_rows else ''})")
         if self.ineqG is not None:
             # the general rows live in the fused team kernel alone (alqp_solve_lin_poly): the launch-per-step helper
             # kernels, k_newton_step* and the compiled-in models know no such rows
@@ -1003,7 +1034,7 @@ class MPC(Module):
                                           "nonlinear-caller kernels and the compiled-in models know no general rows")
             if st.lam.shape[1] != self.neq + self.nineq:
                 raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the general rows need "
-                                 f"{self.neq + self.nineq} = T nx + T (2 nu + m)")
+                                 f"{self.neq + self.nineq} = T nx + T (2 nu{' + 2 nx' if self.x_lower is not None else ''} + m)")
         if self.state_estimator:
             # cost gradient on the states only (al_utils_se.py:300-310) while the Hessian keeps diag(Q) on the
             # controls (:66-68): the kernels' `state_estimator` flag. Their merit still counts the controls' cost

@@ -266,6 +266,34 @@ int alqp_solve_lin_poly_f64(const AlqpDims *dims, const AlqpParams *prm, const v
                             const AlqpTrace *trace, void *stream);
 
 /*
+ * The same solve with TWO OR THREE of the three additions above TOGETHER: the arguments of alqp_solve_lin_*, then those of
+ * a dense cost (C), of state bounds (x_lo, x_hi, sb_x, st_x) and of general rows (G, h, m, sb_g, st_g, sb_h, st_h), each
+ * as its own entry point above takes them. A null pointer means "feature absent", and the non-null set picks the kernel:
+ * C + bounds, C + rows, bounds + rows, or all three. Qd is read only when C is null (and may be null otherwise).
+ * lam is [B][M] with M = T nx + T (2 nu + [2 nx] + [m]): the T nx equality rows, then per stage
+ * [u - u_hi | -u + u_lo | x - x_hi | -x + x_lo | G_t z_t - h_t], a feature's rows present exactly when the feature is.
+ * Team kernel only: workspace / ws_bytes are not read, AlqpParams.variant must be 0 or 1. ALQP_E_BADARG: fewer than two
+ * features present (the entry points above stay the way to run one), one half of a pair null, m outside 1..64 with rows
+ * given, a negative stride, variant 2. ALQP_E_UNSUPPORTED: (nx, nu) is no compiled instance, or the horizon's LDS image
+ * does not fit (that of alqp_solve_lin_poly_* with rows, the team image without). Flags, skip_flag, trace, factor_out and
+ * an empty batch as for the entry points above.
+ */
+int alqp_solve_lin_gen_f32(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                           const void *F, const void *c, const void *x0, const void *u_lo, const void *u_hi,
+                           long sb_u, long st_u, void *z, void *lam, void *rho, void *phi, void *rnorm2,
+                           int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
+                           void *workspace, size_t ws_bytes, void *stream, const void *C, const void *x_lo,
+                           const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,
+                           long sb_g, long st_g, long sb_h, long st_h);
+int alqp_solve_lin_gen_f64(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                           const void *F, const void *c, const void *x0, const void *u_lo, const void *u_hi,
+                           long sb_u, long st_u, void *z, void *lam, void *rho, void *phi, void *rnorm2,
+                           int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
+                           void *workspace, size_t ws_bytes, void *stream, const void *C, const void *x_lo,
+                           const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,
+                           long sb_g, long st_g, long sb_h, long st_h);
+
+/*
  * One Newton direction for the nonlinear-caller mode: the caller evaluated
  * dx_jac(x,u) -> (xnext, F) in PyTorch (al_utils.py:233-248). Replaces
  * merit_grad_hessian (:80-123) + cholesky_ex/cholesky_solve (:510-515).
