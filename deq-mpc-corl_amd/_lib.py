@@ -109,6 +109,16 @@ _SIGS = {
                                 C.POINTER(AlqpBwdDyn), _P]),
     "alqp_merit_pick": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   C.c_long, C.c_long, C.POINTER(AlqpObstacles), _P, _P, _P, _P, _P, _P, _P]),
+    # the launch-per-step operations with state box rows: the plain twin's arguments without the AlqpObstacles, and
+    # x_lo, x_hi, sb_x, st_x behind the control bounds (added under ABI version 17: symbols only)
+    "alqp_newton_step_xbox": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, _P, _P, _P, _P, _P]),
+    "alqp_merit_xbox": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, _P, _P, _P]),
+    "alqp_merit_pick_xbox": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P]),
+    "alqp_dual_update_xbox": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long,
+                                        _P, _P, C.c_long, C.c_long, _P, _P, C.c_double, _P]),
     "alqp_ipm_solve": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpIpmParams), _P, _P, _P, _P, _P, _P, _P,
                                  C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _P, C.c_size_t, _P,
                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

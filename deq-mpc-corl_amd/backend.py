@@ -615,6 +615,85 @@ class HipBackend:
             _ptr(rho, "rho", dt), rho_scale, _stream())
         _lib.check(rc, "alqp_dual_update_" + sfx)
 
+    # -- the same four with state box rows (alqp_*_xbox): MPC(x_lower=, x_upper=) with a callable dx -----------------
+    @staticmethod
+    def _xbox_checks(dims, lam, xbnd):
+        """The host-side checks solve_lin_xbox makes: lam at least M = T nx + T (2 nu + 2 nx) wide, the bounds as long as
+        their strides reach. -> (xlo, xhi, sb_x, st_x)."""
+        B, T, nx, nu = dims
+        xlo, xhi, sb_x, st_x = xbnd
+        M = T * nx + T * (2 * nu + 2 * nx)
+        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
+            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, the state-bound rows need [B, {M}]")
+        for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
+            if t is None:
+                raise ValueError(f"mi_alqp: {name} is required")
+            if min(sb_x, st_x) >= 0 and t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
+                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
+        return xlo, xhi, sb_x, st_x
+
+    def newton_step_xbox(self, dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, d_out,
+                         g_out=None, factor=None, info=None):
+        """newton_step with state box rows (alqp_newton_step_xbox): xbnd = (xlo, xhi, sb_x, st_x) as solve_lin_xbox takes
+        them, lam [B, T nx + T (2 nu + 2 nx)]. The team kernel at any batch (no workspace), optional packed `factor`."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_newton_step_xbox_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt),
+            _ptr(xhi, "x_upper", dt), sb_x, st_x, _ptr(d_out, "d_out", dt), _ptr(g_out, "g_out", dt, True),
+            _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True), _stream())
+        _lib.check(rc, "alqp_newton_step_xbox_" + sfx)
+        self.last_step_kernel = "k_newton_step_xbox"
+
+    def merit_xbox(self, dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, phi, rnorm2=None):
+        """merit with state box rows (alqp_merit_xbox); xbnd and lam as newton_step_xbox."""
+        B, T, nx, nu = dims
+        dt = zc.dtype
+        sfx = _dt(zc)
+        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_merit_xbox_" + sfx)(
+            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt),
+            _ptr(xhi, "x_upper", dt), sb_x, st_x, _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True), _stream())
+        _lib.check(rc, "alqp_merit_xbox_" + sfx)
+
+    def merit_pick_xbox(self, dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, z, phi_prev,
+                        rnorm2=None, phi_all=None, k_out=None, accept_out=None):
+        """merit_pick with state box rows (alqp_merit_pick_xbox); xbnd and lam as newton_step_xbox."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
+        dd = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_merit_pick_xbox_" + sfx)(
+            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt),
+            _ptr(xhi, "x_upper", dt), sb_x, st_x, _ptr(z, "z", dt), _ptr(phi_prev, "phi_prev", dt),
+            _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
+            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
+        _lib.check(rc, "alqp_merit_pick_xbox_" + sfx)
+
+    def dual_update_xbox(self, dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, lam, rho, rho_scale=10.0):
+        """dual_update with state box rows (alqp_dual_update_xbox); xbnd and lam as newton_step_xbox."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_dual_update_xbox_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt),
+            _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt), _ptr(xhi, "x_upper", dt), sb_x, st_x,
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale, _stream())
+        _lib.check(rc, "alqp_dual_update_xbox_" + sfx)
+
     def _backward(self, dims, factor, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, dyn):
         """alqp_backward_*: `factor` or `workspace` is a device pointer, the other None."""
         dt = gbar.dtype

@@ -368,6 +368,29 @@ int newton_step_impl(const AlqpDims *dims, const void *z, const void *xnext, con
     return dispatch_step<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
 }
 
+// One Newton direction with state box rows: the team kernel only (no quad step kernel knows such rows), so no workspace,
+// and the horizon must fit the team's LDS image like alqp_solve_lin_xbox's.
+template <typename real>
+int newton_step_xbox_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *F, const void *x0,
+                          const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                          const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                          long st_x, void *d_out, void *g_out, void *factor_out, int *info, void *stream) {
+    if (!dims_ok(dims) || !z || !xnext || !F || !x0 || !lam || !rho || !Qd || !q || !u_lo || !u_hi || !x_lo || !x_hi ||
+        !d_out)
+        return ALQP_E_BADARG;
+    if (sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
+    const size_t lds = lds_query<real>(dims->nx, dims->nu, dims->T);
+    if (lds == 0 || lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    XboxStepArgs<real> a = {};
+    a.B = dims->B; a.T = dims->T;
+    a.z = (const real *)z; a.xnext = (const real *)xnext; a.F = (const real *)F; a.x0 = (const real *)x0;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
+    a.d_out = (real *)d_out; a.g_out = (real *)g_out; a.factor = (real *)factor_out; a.info = info;
+    return dispatch_step_xbox<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
+}
+
 // fills what the plain and the DYN backward share and launches: quad kernels on a workspace, team kernels on a factor
 template <typename real, bool DYN>
 int launch_backward(const AlqpDims *dims, const void *factor, void *workspace, const void *F, const void *rho,
@@ -548,6 +571,16 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
         return alqp::newton_step_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
                                             st_u, obs, workspace, ws_bytes, d_out, g_out, factor_out, \
                                             info, stream);                                            \
+    }                                                                                                 \
+    int alqp_newton_step_xbox_##SFX(const AlqpDims *dims, const void *z, const void *xnext,           \
+                                    const void *F, const void *x0, const void *lam, const void *rho,  \
+                                    const void *Qd, const void *q, const void *u_lo,                  \
+                                    const void *u_hi, long sb_u, long st_u, const void *x_lo,         \
+                                    const void *x_hi, long sb_x, long st_x, void *d_out, void *g_out, \
+                                    void *factor_out, int *info, void *stream) {                      \
+        return alqp::newton_step_xbox_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi,  \
+                                                 sb_u, st_u, x_lo, x_hi, sb_x, st_x, d_out, g_out,    \
+                                                 factor_out, info, stream);                           \
     }                                                                                                 \
     int alqp_backward_##SFX(const AlqpDims *dims, const void *factor, void *workspace,                \
                             size_t ws_bytes, const void *F, const void *rho, const void *z_final,     \

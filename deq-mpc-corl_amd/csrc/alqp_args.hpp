@@ -167,6 +167,14 @@ struct StepArgs {
     int no_init;       // state-estimator row set (AlqpObstacles.state_estimator)
 };
 
+// The one-step kernel with state box rows (k_newton_step_xbox): the bounds behind the plain arguments, in a type of its own
+// like XboxSolveArgs, so that StepArgs and k_newton_step stay what they were. obs / nobs / obs_r2 / no_init are unused (0).
+template <typename real>
+struct XboxStepArgs : StepArgs<real> {
+    const real *xlo, *xhi;   // [nx] (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx)
+    long sb_x, st_x;
+};
+
 // DYN = false: the plain backward (alqp_backward_* with dyn = NULL), the kernel arguments it always had. DYN = true (a
 // non-null AlqpBwdDyn) adds the gradients w.r.t. the affine dynamics and the initial state behind them, in a type of
 // its own so that the plain kernels' argument block, and with it their code, stays what it was.

@@ -1,5 +1,5 @@
 // alqp_aux.hip - the size-generic helper kernels of the launch-per-step routes (merit, line-search pick, dual update,
-// batch-global exit test; one wavefront per instance) with their C ABI.
+// batch-global exit test; one wavefront per instance) with their C ABI, and the state-bound twins of merit, pick and dual.
 #include <hip/hip_runtime.h>
 
 #include "alqp_launch.hpp"   // dims_ok, set_obstacles
@@ -338,6 +338,244 @@ int dual_impl(const AlqpDims *dims, const void *z, const void *xnext, const void
     return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
 }
 
+// ---- the same three with state box rows xlo[t] <= x_t <= xhi[t] (MPC(x_lower=, x_upper=) with a callable dx) ----------
+// Kernels and an argument type of their own, so that AuxArgs and the kernels above stay what they were. Multipliers per
+// stage [u - uhi | -u + ulo | x - xhi | -x + xlo], stage stride 2 nu + 2 nx (Team's XBOX layout); a bound is addressed
+// b sb_x + t st_x + i. The state rows follow the control rows' conventions: lam * r with the unclamped r plus
+// 0.5 rho max(r, 0)^2 in the merit, max(0, lam + rho r) in the dual update; stage 0 included. No obstacle rows and no
+// state-estimator row set (obs / nobs / obs_r2 / no_init of the base are unused).
+template <typename real>
+struct XboxAuxArgs : AuxArgs<real> {
+    const real *xlo, *xhi;   // [nx] (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx)
+    long sb_x, st_x;
+};
+
+template <typename real>
+__global__ __launch_bounds__(64) void k_merit_xbox(XboxAuxArgs<real> a) {
+    const int lane = threadIdx.x;
+    const int b = blockIdx.x % a.B, kk = blockIdx.x / a.B;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx;
+    const real *z = a.zc + ((size_t)kk * a.B + b) * T * n;
+    const real *xn = a.xnext + ((size_t)kk * a.B + b) * (T - 1) * nx;
+    const int nit = 2 * nu + 2 * nx;   // inequality rows per stage
+    const real *lam = a.lam + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *Qd = a.Qd + (size_t)b * T * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = a.xlo + (size_t)b * a.sb_x, *xhi = a.xhi + (size_t)b * a.sb_x;
+    const real rho = a.rho[b];
+    real acc = 0, sq = 0;
+    for (int e = lane; e < T * n; e += 64) {
+        int t = e / n, j = e - t * n;
+        real v = z[e];
+        acc += (real(0.5) * Qd[e] * v + q[e]) * v;
+        // the element's two box rows: control rows at [0, 2 nu) of the stage, state rows at [2 nu, 2 nu + 2 nx)
+        const bool isu = j >= nx;
+        const int jj = isu ? j - nx : j, w = isu ? nu : nx;
+        const real bh = isu ? uhi[t * a.st_u + jj] : xhi[t * a.st_x + jj];
+        const real bl = isu ? ulo[t * a.st_u + jj] : xlo[t * a.st_x + jj];
+        real vu = v - bh, vl = -v + bl;
+        real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+        int ru = neq + t * nit + (isu ? 0 : 2 * nu) + jj;
+        acc += lam[ru] * vu + lam[ru + w] * vl;
+        sq += cu * cu + cl * cl;
+    }
+    for (int e = lane; e < neq; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        acc += lam[e] * r;
+        sq += r * r;
+    }
+    acc = wave_sum(acc);
+    sq = wave_sum(sq);
+    if (lane == 0) {
+        a.phi[(size_t)kk * a.B + b] = acc + real(0.5) * rho * sq;
+        if (a.rnorm2) a.rnorm2[(size_t)kk * a.B + b] = sq;
+    }
+}
+
+// k_merit_pick with the state rows: a state element gets what a control element gets, its two bounds and two multipliers
+// loaded once and all 20 candidates from registers.
+template <typename real>
+__global__ __launch_bounds__(64) void k_merit_pick_xbox(XboxAuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, nit = 2 * nu + 2 * nx;
+    real *z = a.z + (size_t)b * T * n;
+    const real *d = a.d + (size_t)b * T * n;
+    const real *lam = a.lam + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *Qd = a.Qd + (size_t)b * T * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = a.xlo + (size_t)b * a.sb_x, *xhi = a.xhi + (size_t)b * a.sb_x;
+    const real rho = a.rho[b];
+    real acc[20], sq[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) { acc[k] = 0; sq[k] = 0; }
+    // cost + box rows (controls and states): every lane walks its elements once, all candidates from registers
+    for (int e = lane; e < T * n; e += 64) {
+        const int t = e / n, j = e - t * n;
+        const real zv = z[e], dv = d[e], Qv = Qd[e], qv = q[e];
+        const bool isu = j >= nx;
+        const int jj = isu ? j - nx : j, w = isu ? nu : nx;
+        const int ru = neq + t * nit + (isu ? 0 : 2 * nu) + jj;
+        const real bu = isu ? uhi[t * a.st_u + jj] : xhi[t * a.st_x + jj];
+        const real bl = isu ? ulo[t * a.st_u + jj] : xlo[t * a.st_x + jj];
+        const real lu = lam[ru], ll = lam[ru + w];
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            const real v = zv + alpha * dv;
+            acc[k] += (real(0.5) * Qv * v + qv) * v;
+            const real vu = v - bu, vl = -v + bl;
+            const real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+            acc[k] += lu * vu + ll * vl;
+            sq[k] += cu * cu + cl * cl;
+            alpha *= real(0.5);
+        }
+    }
+    // equality rows: r = x_{t+1}(candidate) - xnext_k, init rows x_0 - x0
+    for (int e = lane; e < neq; e += 64) {
+        const int t = e / nx, i = e - t * nx;
+        const real le = lam[e];
+        const int zi = (t < T - 1) ? (t + 1) * n + i : i;
+        const real zv = z[zi], dv = d[zi];
+        const real x0v = (t < T - 1) ? real(0) : a.x0[(size_t)b * nx + i];
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            if (k < a.n_ls) {
+                const real ref = (t < T - 1) ? a.xnext[(((size_t)k * a.B + b) * (T - 1) + t) * nx + i] : x0v;
+                const real r = zv + alpha * dv - ref;
+                acc[k] += le * r;
+                sq[k] += r * r;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    int kbest = 0;
+    real best = 0, sqbest = 0;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) {
+        if (k < a.n_ls) {
+            const real s2 = wave_sum(sq[k]);
+            const real v = wave_sum(acc[k]) + real(0.5) * rho * s2;
+            if (a.phi) a.phi[(size_t)k * a.B + b] = v;     // (all lanes hold the same value)
+            if (k == 0) { best = v; sqbest = s2; }
+            else if (!(best != best) && (v != v || v < best)) { best = v; kbest = k; sqbest = s2; }
+        }
+    }
+    const real prev = a.phi_prev[b];
+    const bool ok = best < prev;
+    if (ok) {
+        const real alpha = real(1) / real(1 << kbest);
+        for (int e = lane; e < T * n; e += 64) z[e] += alpha * d[e];
+    }
+    if (lane == 0) {
+        a.phi_prev[b] = best;
+        if (a.k_out) a.k_out[b] = kbest;
+        if (a.accept_out) a.accept_out[b] = ok ? 1 : 0;
+        if (a.rnorm2 && ok) a.rnorm2[b] = sqbest;
+    }
+}
+
+template <typename real>
+__global__ __launch_bounds__(64) void k_dual_xbox(XboxAuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx;
+    const real *z = a.zc + (size_t)b * T * n;
+    const real *xn = a.xnext + (size_t)b * (T - 1) * nx;
+    const int nit = 2 * nu + 2 * nx;
+    real *lam = a.lam_io + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = a.xlo + (size_t)b * a.sb_x, *xhi = a.xhi + (size_t)b * a.sb_x;
+    const real rho = a.rho_io[b];
+    for (int e = lane; e < neq; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        lam[e] += rho * r;
+    }
+    for (int e = lane; e < T * nu; e += 64) {
+        int t = e / nu, j = e - t * nu;
+        real u = z[t * n + nx + j];
+        int ru = neq + t * nit + j, rl = ru + nu;
+        real v1 = lam[ru] + rho * (u - uhi[t * a.st_u + j]);
+        real v2 = lam[rl] + rho * (-u + ulo[t * a.st_u + j]);
+        lam[ru] = v1 < 0 ? real(0) : v1;
+        lam[rl] = v2 < 0 ? real(0) : v2;
+    }
+    for (int e = lane; e < T * nx; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real x = z[t * n + i];
+        int ru = neq + t * nit + 2 * nu + i, rl = ru + nx;
+        real v1 = lam[ru] + rho * (x - xhi[t * a.st_x + i]);
+        real v2 = lam[rl] + rho * (-x + xlo[t * a.st_x + i]);
+        lam[ru] = v1 < 0 ? real(0) : v1;
+        lam[rl] = v2 < 0 ? real(0) : v2;
+    }
+    __syncthreads();
+    if (lane == 0) a.rho_io[b] = rho * a.rho_scale;
+}
+
+// what the three entry points below fill alike; false: ALQP_E_BADARG
+template <typename real>
+bool set_xbox_aux(const AlqpDims *dims, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                  const void *x_lo, const void *x_hi, long sb_x, long st_x, XboxAuxArgs<real> &a) {
+    if (!dims_ok(dims) || !x0 || !u_lo || !u_hi || !x_lo || !x_hi || sb_x < 0 || st_x < 0) return false;
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu;
+    a.x0 = (const real *)x0;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
+    return true;
+}
+
+template <typename real>
+int merit_xbox_impl(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                    const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                    const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                    long st_x, void *phi, void *rnorm2, void *stream) {
+    XboxAuxArgs<real> a = {};
+    if (!set_xbox_aux<real>(dims, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, a) || K < 1 || !zc || !xnext ||
+        !lam || !rho || !Qd || !q || !phi)
+        return ALQP_E_BADARG;
+    a.K = K;
+    a.zc = (const real *)zc; a.xnext = (const real *)xnext;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.phi = (real *)phi; a.rnorm2 = (real *)rnorm2;
+    hipLaunchKernelGGL(k_merit_xbox<real>, dim3((unsigned)((size_t)K * dims->B)), dim3(64), 0,
+                       (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int merit_pick_xbox_impl(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                         const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                         const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                         long st_x, void *z, void *phi_prev, void *rnorm2, void *phi_all, int *k_out,
+                         int *accept_out, void *stream) {
+    XboxAuxArgs<real> a = {};
+    if (!set_xbox_aux<real>(dims, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, a) || n_ls < 1 || n_ls > 20 ||
+        !d || !xnext_all || !lam || !rho || !Qd || !q || !z || !phi_prev)
+        return ALQP_E_BADARG;
+    a.n_ls = n_ls;
+    a.d = (const real *)d; a.xnext = (const real *)xnext_all;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.z = (real *)z; a.phi_prev = (real *)phi_prev; a.rnorm2 = (real *)rnorm2; a.phi = (real *)phi_all;
+    a.k_out = k_out; a.accept_out = accept_out;
+    hipLaunchKernelGGL(k_merit_pick_xbox<real>, dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int dual_xbox_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *x0, const void *u_lo,
+                   const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                   void *lam, void *rho, double rho_scale, void *stream) {
+    XboxAuxArgs<real> a = {};
+    if (!set_xbox_aux<real>(dims, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, a) || !z || !xnext || !lam || !rho)
+        return ALQP_E_BADARG;
+    a.zc = (const real *)z; a.xnext = (const real *)xnext;
+    a.lam_io = (real *)lam; a.rho_io = (real *)rho; a.rho_scale = (real)rho_scale;
+    hipLaunchKernelGGL(k_dual_xbox<real>, dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
 }  // namespace alqp
 
 extern "C" {
@@ -376,6 +614,34 @@ int alqp_exit_test(const double *sumsq, double *ctl, int mode, double tol, void 
                                double rho_scale, void *stream) {                                      \
         return alqp::dual_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, obs, lam, rho,       \
                                      rho_scale, stream);                                              \
+    }                                                                                                 \
+    int alqp_merit_xbox_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,         \
+                              const void *x0, const void *lam, const void *rho, const void *Qd,       \
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u,           \
+                              long st_u, const void *x_lo, const void *x_hi, long sb_x, long st_x,    \
+                              void *phi, void *rnorm2, void *stream) {                                \
+        return alqp::merit_xbox_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
+                                           st_u, x_lo, x_hi, sb_x, st_x, phi, rnorm2, stream);        \
+    }                                                                                                 \
+    int alqp_merit_pick_xbox_##SFX(const AlqpDims *dims, int n_ls, const void *d,                     \
+                                   const void *xnext_all, const void *x0, const void *lam,            \
+                                   const void *rho, const void *Qd, const void *q, const void *u_lo,  \
+                                   const void *u_hi, long sb_u, long st_u, const void *x_lo,          \
+                                   const void *x_hi, long sb_x, long st_x, void *z, void *phi_prev,   \
+                                   void *rnorm2, void *phi_all, int *k_out, int *accept_out,          \
+                                   void *stream) {                                                    \
+        return alqp::merit_pick_xbox_impl<REAL>(dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, u_lo,  \
+                                                u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, z,          \
+                                                phi_prev, rnorm2, phi_all, k_out, accept_out,         \
+                                                stream);                                              \
+    }                                                                                                 \
+    int alqp_dual_update_xbox_##SFX(const AlqpDims *dims, const void *z, const void *xnext,           \
+                                    const void *x0, const void *u_lo, const void *u_hi, long sb_u,    \
+                                    long st_u, const void *x_lo, const void *x_hi, long sb_x,         \
+                                    long st_x, void *lam, void *rho, double rho_scale,                \
+                                    void *stream) {                                                   \
+        return alqp::dual_xbox_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi,     \
+                                          sb_x, st_x, lam, rho, rho_scale, stream);                   \
     }
 
 ALQP_DEFINE_AUX(f32, float)

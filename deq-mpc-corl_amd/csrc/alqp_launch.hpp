@@ -74,6 +74,8 @@ int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const Tr
 template <typename real>
 int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
+int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream);   // the state-bound unit
+template <typename real>
 int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);

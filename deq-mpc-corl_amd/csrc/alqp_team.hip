@@ -31,6 +31,7 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // called through one, every plain instantiation came out with different register allocation.
 // The state-bound unit (-DALQP_XBOX_UNIT) is made the same way, a third header: k_solve_lin_xbox, state box rows
 // xlo <= x_t <= xhi behind every stage's control rows (Team's XBOX flag), the bounds at a.xlo / a.xhi; uncapped builds only.
+// That unit also holds k_newton_step_xbox, the one-step kernel below over the same Team (state bounds with a callable dx).
 // The general-row unit (-DALQP_POLY_UNIT), a fourth header: k_solve_lin_poly, a.m rows G_t z_t <= h_t behind every stage's
 // control rows (Team's POLY flag), rows and right-hand sides at a.G / a.h. Its LDS image is the team image plus a hand-over
 // region of 2 pad4(a.m) words per team. Uncapped builds only, for the reason given above: a capped build spills, and a
@@ -329,6 +330,56 @@ __global__ __launch_bounds__(64) void k_newton_step(StepArgs<real> a) {
     }
 }
 
+#ifdef ALQP_XBOX_UNIT
+// The same with state box rows (the state-bound unit only): k_newton_step's body over Team<.., XBOX>, the bounds at
+// gxlo / gxhi, multipliers per stage [u | x] (M = T nx + T (2 nu + 2 nx) per instance). No obstacle rows and no
+// state-estimator row set: forward_sweep's obstacle offset is written without XR.
+template <typename real, int NX, int NU>
+__global__ __launch_bounds__(64) void k_newton_step_xbox(XboxStepArgs<real> a) {
+    using C = Cfg<real, NX, NU>;
+    constexpr int G = C::G, N = C::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    real *smem = reinterpret_cast<real *>(smem_raw);
+    const int lane = threadIdx.x, team = lane / G, li = lane % G;
+    const int b_raw = blockIdx.x * C::QPW + team;
+    const bool active = b_raw < a.B;
+    const int b = active ? b_raw : a.B - 1;
+    const int T = a.T;
+    const size_t M = (size_t)C::M(T) + (size_t)2 * T * NX;
+
+    Team<real, NX, NU, false, true> tm;
+    tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
+    tm.gQd = a.Qd + (size_t)b * T * N;
+    tm.gq = a.q + (size_t)b * T * N;
+    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
+    tm.gc = nullptr;
+    tm.gx0 = a.x0 + (size_t)b * NX;
+    tm.gulo = a.ulo + (size_t)b * a.sb_u;
+    tm.guhi = a.uhi + (size_t)b * a.sb_u;
+    tm.st_u = a.st_u;
+    tm.gxlo = a.xlo + (size_t)b * a.sb_x;
+    tm.gxhi = a.xhi + (size_t)b * a.sb_x;
+    tm.st_x = a.st_x;
+    tm.gxnext = a.xnext + (size_t)b * (T - 1) * NX;
+    const real *gz = a.z + (size_t)b * T * N;
+    tm.lams = const_cast<real *>(a.lam) + (size_t)b * M;  // read-only here
+    for (int e = li; e < T * N; e += G) tm.zs[e] = gz[e];
+    tm.rho = a.rho[b];
+    wave_sync();
+    tm.forward_sweep((active && a.g_out) ? a.g_out + (size_t)b * T * N : nullptr);
+    tm.backward_sweep();
+    if (active) {
+        real *gd = a.d_out + (size_t)b * T * N;
+        for (int e = li; e < T * N; e += G) gd[e] = tm.ds[e];
+        if (a.factor) {
+            real *gf = a.factor + (size_t)b * T * C::XT;
+            for (int e = li; e < T * C::XT; e += G) gf[e] = tm.Xp[e];
+        }
+        if (li == 0 && a.info && tm.info && a.info[b] == 0) a.info[b] = tm.info;
+    }
+}
+#endif
+
 // ---- backward of the implicit layer -------------------------------------------------
 // DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_* with an AlqpBwdDyn). With
 // w = -H^{-1} gbar in ds, s_t = w_{t+1}[x] - F_t w_t in seq (what backward_sweep leaves there as (J d)_eq) and
@@ -502,6 +553,13 @@ int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const Trac
         return launch_team_kernel<real, NX, NU>(k_solve_lin_xbox<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
     });
 }
+
+template <typename real>
+int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        return launch_team_kernel<real, NX, NU>(k_newton_step_xbox<real, NX, NU>, a.B, a.T, stream, a);
+    });
+}
 #endif
 
 template <typename real, bool DYN>
@@ -533,6 +591,8 @@ template int dispatch_solve_poly<double>(int, int, const PolySolveArgs<double> &
 #elif defined(ALQP_XBOX_UNIT)
 template int dispatch_solve_xbox<float>(int, int, const XboxSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_xbox<double>(int, int, const XboxSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+template int dispatch_step_xbox<float>(int, int, const XboxStepArgs<float> &, hipStream_t);
+template int dispatch_step_xbox<double>(int, int, const XboxStepArgs<double> &, hipStream_t);
 #elif defined(ALQP_DENSE_UNIT)
 template int dispatch_solve_dense<float>(int, int, const DenseSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_dense<double>(int, int, const DenseSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);

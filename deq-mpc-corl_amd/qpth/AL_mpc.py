@@ -169,18 +169,30 @@ class _Launcher:
                                     st.rho, self.phi, info=self.info if info else None, workspace=self.nlws,
                                     **self._out, **kw)
 
+    # The PyTorch-dynamics route's four launches. With state bounds (xbnd) each goes to its _xbox twin, which takes xbnd
+    # behind the control bounds and knows no obstacle rows (the guards of MPC._run keep those apart).
     def merit(self, z, xn, **okw):
+        if self.xbnd is not None:
+            return self.be.merit_xbox(self.dims, 1, z, xn, *self._problem, self.xbnd, self.phi, self.rn2, **okw)
         self.be.merit(self.dims, 1, z, xn, *self._problem, self.phi, self.rn2, **okw)
 
     def newton_step(self, z, xn, F, **kw):
+        if self.xbnd is not None:
+            return self.be.newton_step_xbox(self.dims, z, xn, F, *self._problem, self.xbnd, self.d, **kw)
         self.be.newton_step(self.dims, z, xn, F, *self._problem, self.d, **kw)
 
     def merit_pick(self, xn_all, z, **okw):
+        if self.xbnd is not None:
+            return self.be.merit_pick_xbox(self.dims, N_LS, self.d, xn_all, *self._problem, self.xbnd, z, self.phi,
+                                           rnorm2=self.rn2, k_out=self.k, accept_out=self.acc, **okw)
         self.be.merit_pick(self.dims, N_LS, self.d, xn_all, *self._problem, z, self.phi, rnorm2=self.rn2,
                            k_out=self.k, accept_out=self.acc, **okw)
 
     def dual_update(self, xn, **okw):
         st = self.st
+        if self.xbnd is not None:
+            return self.be.dual_update_xbox(self.dims, st.z, xn, *self._x0_bounds, self.xbnd, st.lam, st.rho, RHO_SCALE,
+                                            **okw)
         self.be.dual_update(self.dims, st.z, xn, *self._x0_bounds, st.lam, st.rho, RHO_SCALE, **okw)
 
 
@@ -318,9 +330,14 @@ class MPC(Module):
     anything that broadcasts to [B,T,nx] (per-stage bounds can relax stage 0, whose state is pinned to x0). A non-finite
     entry means "no bound". The reference carries the two arguments but never built their rows (al_utils.py:294-302
     are commented out). ``lamda_prev`` is then [B, T nx + T (2 nu + 2 nx)]: the equality rows, then per stage
-    [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower]. LinDx routes only (the fused team kernel, at any
-    batch): not with a callable ``dx``, ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``.
-    All gradients above stay available, taken with the active set held fixed.
+    [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower]. With ``LinDx`` the fused team kernel runs, at any batch.
+    With a callable ``dx`` / ``dx_jac`` the PyTorch-dynamics route runs with the state-bound twins of
+    its four kernels (``HipBackend.newton_step_xbox``, ``merit_xbox``, ``merit_pick_xbox``, ``dual_update_xbox``): the
+    direction comes from the team kernel at any batch, and a provider with a compiled-in model (``PendulumDynamics``,
+    ...) takes this route too. A backend without ``newton_step_xbox`` raises ``NotImplementedError`` for a callable
+    ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``, and on the callable route not with
+    ``diag_cost=False`` or ``ineqG``. The gradients of the route in use stay available (callable ``dx``: ``q`` and
+    ``diag(C)``), taken with the active set held fixed.
 
     ``ineqG`` / ``ineqh`` (both or neither): m >= 1 general linear rows G_t tau_t <= h_t per stage, on all
     T stages next to the control bounds. ``ineqG`` is [m,n], [T,m,n] or [B,T,m,n], ``ineqh`` [m], [T,m] or [B,T,m]
@@ -361,10 +378,11 @@ class MPC(Module):
         # is asked now, the default one (resolved lazily) in the guard block of the solve
         no_gen = backend is not None and not hasattr(backend, "solve_lin_gen")
         if x_lower is not None:
-            # the state-bound rows live in the fused team kernel of the LinDx routes alone (alqp_solve_lin_xbox)
+            # the state-bound rows live in the fused team kernel of the LinDx routes (alqp_solve_lin_xbox) and in the
+            # _xbox twins of the launch-per-step kernels (a callable dx), which have no state-estimator row set
             if state_estimator:
-                raise NotImplementedError("MPC: x_lower / x_upper with state_estimator: that variant runs on the "
-                                          "nonlinear-caller kernels, which know no state-bound rows")
+                raise NotImplementedError("MPC: x_lower / x_upper with state_estimator: the state-bound variants of the "
+                                          "nonlinear-caller kernels have no state-estimator row set")
             if not diag_cost and no_gen:
                 raise NotImplementedError(_NO_DENSE_XBOX)
         if ineqG is not None or ineqh is not None:
@@ -813,10 +831,11 @@ class MPC(Module):
 
     def _fused_model(self, st):
         """True when the dynamics model is compiled into the library (dynamics.py) and this solve may take it: plain
-        row set, one call per solve (not the stream loop), the sizes it was compiled for, and the model's default
-        route unless `prefer_fused`."""
+        row set (the compiled-in models know no state-bound rows: with x_lower / x_upper a provider such as
+        PendulumDynamics takes the PyTorch-dynamics route), one call per solve (not the stream loop), the sizes it was
+        compiled for, and the model's default route unless `prefer_fused`."""
         dx = st.dx
-        return (st.lin is None and not st.stream_mode and not self._has_extra_rows()
+        return (st.lin is None and not st.stream_mode and not self._has_extra_rows() and self.x_lower is None
                 and getattr(dx, "fused_id", None) is not None
                 and (getattr(dx, "fused_default", True) or self.prefer_fused)
                 and (getattr(dx, "nx", None), getattr(dx, "nu", None)) == (self.n_state, self.n_ctrl))
@@ -851,8 +870,10 @@ class MPC(Module):
         alphas = (2.0 ** -torch.arange(N_LS, device=z.device, dtype=z.dtype)).view(N_LS, 1, 1, 1)
         # from B = QUAD_MIN_BATCH on the direction comes from the quad kernels (obstacle rows / the state-estimator
         # row set included), whose factor stays in the workspace records: the private one when backward follows
+        # With state bounds the direction comes from the team kernel at any batch (no quad step kernel knows those rows):
+        # no workspace is fetched, and the packed factor is the saved one.
         qws = L.qws   # (fetched once per solve, on the assumption L.lin_tracked states)
-        if qws is None and L.cached_ws is not None and L.dims[0] >= L.quad_min_batch:
+        if qws is None and L.cached_ws is not None and L.dims[0] >= L.quad_min_batch and L.xbnd is None:
             qws = L.cached_ws(L.dims, z)[0]
         steps = 0
         while steps < MAX_NEWTON:
@@ -1006,15 +1027,16 @@ class MPC(Module):
                 raise NotImplementedError("MPC: diag_cost=False needs affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models read diag(C)")
         if self.x_lower is not None:
-            # the state-bound rows live in the fused team kernel alone (alqp_solve_lin_xbox): the launch-per-step helper
-            # kernels, k_newton_step* and the compiled-in models know no such rows
+            # the state-bound rows live in the fused team kernel (alqp_solve_lin_xbox) and, for a callable dx, in the
+            # launch-per-step kernels' _xbox twins; the quad step kernels, the obstacle /
+            # state-estimator row sets and the compiled-in models know no such rows
             if self._has_extra_rows():
-                raise NotImplementedError("MPC: x_lower / x_upper with obstacle rows (Obstacle_MPC): those run on the "
-                                          "nonlinear-caller kernels, which know no state-bound rows")
+                raise NotImplementedError("MPC: x_lower / x_upper with obstacle rows (Obstacle_MPC): the state-bound "
+                                          "variants of the nonlinear-caller kernels take no obstacle rows")
             if self.linearize_once:
                 raise NotImplementedError("MPC: x_lower / x_upper with linearize_once: the frozen-linearisation route "
-                                          "evaluates merit and dual update with kernels that know no state-bound rows")
-            if st.lin is None:
+                                          "is not built with state-bound rows")
+            if st.lin is None and not hasattr(be, "newton_step_xbox"):
                 raise NotImplementedError("MPC: x_lower / x_upper need affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models know no state-bound rows")
             if st.lam.shape[1] != self.neq + self.nineq:

@@ -35,8 +35,8 @@ class Obstacle_MPC(MPC):
             raise NotImplementedError("Obstacle_MPC: diag_cost=False is not built (the obstacle rows exist in the "
                                       "nonlinear-caller kernels only, which read diag(C))")
         if self.x_lower is not None:
-            raise NotImplementedError("Obstacle_MPC: x_lower / x_upper are not built (the obstacle rows exist in the "
-                                      "nonlinear-caller kernels only, which know no state-bound rows)")
+            raise NotImplementedError("Obstacle_MPC: x_lower / x_upper are not built (the state-bound variants of the "
+                                      "nonlinear-caller kernels take no obstacle rows)")
         if self.ineqG is not None:
             raise NotImplementedError("Obstacle_MPC: ineqG / ineqh are not built (the obstacle rows exist in the "
                                       "nonlinear-caller kernels only, which know no general rows)")

@@ -368,6 +368,60 @@ int alqp_dual_update_f64(const AlqpDims *dims, const void *z, const void *xnext,
                          void *lam, void *rho, double rho_scale, void *stream);
 
 /*
+ * The four launch-per-step operations above with the state box rows of alqp_solve_lin_xbox_* (x_lo[t] <= x_t <= x_hi[t] on
+ * all T stages, stage 0 included): state bounds with a caller-evaluated nonlinear model. Each takes its plain twin's
+ * arguments without the AlqpObstacles (no obstacle rows, no state-estimator row set), with x_lo, x_hi, sb_x, st_x right
+ * behind the control bounds: element (b,t,i) at b*sb_x + t*st_x + i, finite, [nx] (0, 0) or [B][T][nx] (T nx, nx).
+ *   lam [B][T*nx + T*(2nu + 2nx)]: per stage [u - u_hi | -u + u_lo | x - x_hi | -x + x_lo] behind the equality rows.
+ * A state row follows the control rows' conventions: lam * r with the unclamped r plus rho/2 max(r, 0)^2 in the merit,
+ * rho on the diagonal of H_tt while r >= 0, max(0, lam + rho r) in the dual update.
+ * alqp_newton_step_xbox_*: the team kernel only - no workspace argument; the packed factor_out is what alqp_backward_*
+ * takes. ALQP_E_UNSUPPORTED for an (nx, nu) that is not compiled and for a horizon whose LDS image does not fit
+ * (alqp_supported_variant(dims, is_f64, 1) == 0); ALQP_E_BADARG for a null bound, a negative stride, an empty batch, and
+ * for n_ls outside 1..20 in alqp_merit_pick_xbox_*.
+ * These symbols were ADDED under ABI version 17 (no existing signature changed, so the number did not move): a caller
+ * that may meet an older library of version 17 detects them by symbol lookup.
+ */
+int alqp_newton_step_xbox_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
+                              const void *x0, const void *lam, const void *rho, const void *Qd,
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              void *d_out, void *g_out, void *factor_out, int *info, void *stream);
+int alqp_newton_step_xbox_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
+                              const void *x0, const void *lam, const void *rho, const void *Qd,
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              void *d_out, void *g_out, void *factor_out, int *info, void *stream);
+int alqp_merit_xbox_f32(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                        const void *lam, const void *rho, const void *Qd, const void *q,
+                        const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                        const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                        void *phi, void *rnorm2, void *stream);
+int alqp_merit_xbox_f64(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                        const void *lam, const void *rho, const void *Qd, const void *q,
+                        const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                        const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                        void *phi, void *rnorm2, void *stream);
+int alqp_merit_pick_xbox_f32(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                             const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                             const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                             long sb_x, long st_x, void *z, void *phi_prev, void *rnorm2, void *phi_all,
+                             int *k_out, int *accept_out, void *stream);
+int alqp_merit_pick_xbox_f64(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                             const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                             const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                             long sb_x, long st_x, void *z, void *phi_prev, void *rnorm2, void *phi_all,
+                             int *k_out, int *accept_out, void *stream);
+int alqp_dual_update_xbox_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
+                              const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              void *lam, void *rho, double rho_scale, void *stream);
+int alqp_dual_update_xbox_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
+                              const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              void *lam, void *rho, double rho_scale, void *stream);
+
+/*
  * Backward of the implicit layer (NewtonAL.backward, al_utils.py:578-615):
  * w = -H^{-1} gbar with the saved factor; q_grad = w, Qd_grad = w * z_final.
  * rho is the penalty the factor was built with. Exactly one of `factor` and `workspace` is non-null:
