@@ -68,6 +68,7 @@ ERRORS = {-1: "bad argument", -2: "unsupported (nx, nu), or horizon / batch beyo
           -3: "kernel launch failed", -4: "grid too large for a cooperative launch"}
 
 _P = C.c_void_p
+_ROWS = (_P, _P, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long)   # G, h, m, sb_g, st_g, sb_h, st_h
 _SIGS = {
     # name: (restype, argtypes) ; the f32/f64 pairs share a signature
     "alqp_solve_nonlin": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), C.c_int, C.c_double, _P, _P, _P, _P, _P,
@@ -119,6 +120,16 @@ _SIGS = {
                                        C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P]),
     "alqp_dual_update_xbox": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long,
                                         _P, _P, C.c_long, C.c_long, _P, _P, C.c_double, _P]),
+    # the same with general rows: G, h, m, sb_g, st_g, sb_h, st_h behind the state-bound arguments (x_lo, x_hi nullable)
+    "alqp_newton_step_rows": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, _P, _P, _P]),
+    "alqp_merit_rows": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, _P]),
+    "alqp_merit_pick_rows": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS,
+                                       _P, _P, _P, _P, _P, _P, _P]),
+    "alqp_dual_update_rows": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long,
+                                        _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, C.c_double, _P]),
     "alqp_ipm_solve": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpIpmParams), _P, _P, _P, _P, _P, _P, _P,
                                  C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _P, C.c_size_t, _P,
                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

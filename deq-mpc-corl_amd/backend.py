@@ -694,6 +694,99 @@ class HipBackend:
             _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale, _stream())
         _lib.check(rc, "alqp_dual_update_xbox_" + sfx)
 
+    # -- the same four with general rows, with or without state box rows (alqp_*_rows): MPC(ineqG=, ineqh=) with a
+    # callable dx ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _rows_checks(dims, lam, xbnd, poly):
+        """The host-side checks solve_lin_poly / solve_lin_gen make: lam at least M = T nx + T (2 nu + [2 nx] + m) wide,
+        bounds and rows as long as their strides reach. -> (xlo, xhi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h)."""
+        B, T, nx, nu = dims
+        n = nx + nu
+        xlo, xhi, sb_x, st_x = xbnd if xbnd is not None else (None, None, 0, 0)
+        G, h, m, sb_g, st_g, sb_h, st_h = poly
+        M = T * nx + T * (2 * nu + (2 * nx if xbnd is not None else 0) + max(int(m), 0))
+        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
+            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, these rows need [B, {M}]")
+        if xbnd is not None:
+            for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
+                if t is None:
+                    raise ValueError(f"mi_alqp: {name} is required")
+                if min(sb_x, st_x) >= 0 and t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
+                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
+        for t, name, sb, st, w in ((G, "ineqG", sb_g, st_g, m * n), (h, "ineqh", sb_h, st_h, m)):
+            if t is not None and m >= 1 and min(sb, st) >= 0 and t.numel() < (B - 1) * sb + (T - 1) * st + w:
+                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
+        return xlo, xhi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h
+
+    @staticmethod
+    def _rows_cargs(rows, dt):
+        """_rows_checks' tuple as the C arguments from x_lo to st_h."""
+        xlo, xhi, sb_x, st_x, G, h, *rest = rows
+        return (_ptr(xlo, "x_lower", dt, True), _ptr(xhi, "x_upper", dt, True), sb_x, st_x,
+                _ptr(G, "ineqG", dt, True), _ptr(h, "ineqh", dt, True), *rest)
+
+    def newton_step_rows(self, dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out,
+                         g_out=None, factor=None, info=None):
+        """newton_step with general rows (alqp_newton_step_rows): poly = (G, h, m, sb_g, st_g, sb_h, st_h) as
+        solve_lin_poly takes them, xbnd = (xlo, xhi, sb_x, st_x) or None (no state bounds),
+        lam [B, T nx + T (2 nu + [2 nx] + m)]. The team kernel at any batch (no workspace), optional packed `factor`."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_newton_step_rows_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(d_out, "d_out", dt),
+            _ptr(g_out, "g_out", dt, True), _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True),
+            _stream())
+        _lib.check(rc, "alqp_newton_step_rows_" + sfx)
+        self.last_step_kernel = "k_newton_step_rows"
+
+    def merit_rows(self, dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2=None):
+        """merit with general rows (alqp_merit_rows); xbnd, poly and lam as newton_step_rows."""
+        B, T, nx, nu = dims
+        dt = zc.dtype
+        sfx = _dt(zc)
+        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_merit_rows_" + sfx)(
+            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(phi, "phi", dt),
+            _ptr(rnorm2, "rnorm2", dt, True), _stream())
+        _lib.check(rc, "alqp_merit_rows_" + sfx)
+
+    def merit_pick_rows(self, dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
+                        phi_prev, rnorm2=None, phi_all=None, k_out=None, accept_out=None):
+        """merit_pick with general rows (alqp_merit_pick_rows); xbnd, poly and lam as newton_step_rows."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
+        dd = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_merit_pick_rows_" + sfx)(
+            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(z, "z", dt),
+            _ptr(phi_prev, "phi_prev", dt), _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
+            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
+        _lib.check(rc, "alqp_merit_pick_rows_" + sfx)
+
+    def dual_update_rows(self, dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, poly, lam, rho, rho_scale=10.0):
+        """dual_update with general rows (alqp_dual_update_rows); xbnd, poly and lam as newton_step_rows."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_dual_update_rows_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt),
+            _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale,
+            _stream())
+        _lib.check(rc, "alqp_dual_update_rows_" + sfx)
+
     def _backward(self, dims, factor, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, dyn):
         """alqp_backward_*: `factor` or `workspace` is a device pointer, the other None."""
         dt = gbar.dtype

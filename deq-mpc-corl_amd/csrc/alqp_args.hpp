@@ -175,6 +175,16 @@ struct XboxStepArgs : StepArgs<real> {
     long sb_x, st_x;
 };
 
+// The one-step kernel with general rows G_t z_t <= h_t (k_newton_step_rows<.., XBOX>): the rows behind XboxStepArgs, with
+// PolySolveArgs' strides. The state bounds are read only by the XBOX instantiations (null otherwise).
+template <typename real>
+struct RowsStepArgs : XboxStepArgs<real> {
+    const real *G, *h;   // G: [m][n] (sb_g = st_g = 0), [T][m][n] (0, m n) or [B][T][m][n] (T m n, m n); h likewise without [n]
+    int m;               // rows per stage, 1 .. 64
+    long sb_g, st_g;
+    long sb_h, st_h;
+};
+
 // DYN = false: the plain backward (alqp_backward_* with dyn = NULL), the kernel arguments it always had. DYN = true (a
 // non-null AlqpBwdDyn) adds the gradients w.r.t. the affine dynamics and the initial state behind them, in a type of
 // its own so that the plain kernels' argument block, and with it their code, stays what it was.

@@ -1,5 +1,6 @@
 // alqp_aux.hip - the size-generic helper kernels of the launch-per-step routes (merit, line-search pick, dual update,
-// batch-global exit test; one wavefront per instance) with their C ABI, and the state-bound twins of merit, pick and dual.
+// batch-global exit test; one wavefront per instance) with their C ABI, and the state-bound twins of merit, pick and dual,
+// and their twins with general rows (with or without state bounds).
 #include <hip/hip_runtime.h>
 
 #include "alqp_launch.hpp"   // dims_ok, set_obstacles
@@ -576,6 +577,330 @@ int dual_xbox_impl(const AlqpDims *dims, const void *z, const void *xnext, const
     return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
 }
 
+// ---- the same three with general rows G_t z_t <= h_t, with or without state box rows (MPC(ineqG=, ineqh=) with a callable
+// dx) -------------------------------------------------------------------------------------------------------------------
+// Again kernels and an argument type of their own. Multipliers per stage [u - uhi | -u + ulo | (x - xhi | -x + xlo) | G_t z_t
+// - h_t], stage stride 2 nu + XR + m with XR = 2 nx when there are state bounds and 0 when there are none (Team's XBOX / POLY
+// layout); XB is a template flag, so the choice is wave-uniform and costs the other build nothing. Row k of stage t of
+// instance b is read in place at G + b sb_g + t st_g + k n, its right-hand side at h + b sb_h + t st_h + k. A row follows the
+// box rows' conventions (tests/poly_rows_reference.py:poly_rows): lam_k r_k with the unclamped r_k = G_k . z_t - h_k plus
+// rho/2 max(r_k, 0)^2 in the merit, max(r_k, 0)^2 in rnorm2, max(0, lam_k + rho r_k) in the dual update.
+// Lanes and rows: a lane per row (row e = t m + k to lane e mod 64), the n-long dot product inside the lane in the order
+// j = 0 .. n-1. n is at most 17 at the compiled sizes, so spreading one row over lanes would leave three quarters of the
+// wavefront idle and pay a cross-lane reduction per row, and the sum's order would depend on the lane split; with a lane per
+// row the 64 lanes read 64 consecutive rows of a stage's [m][n] block, n loads of stride n words that together use every
+// byte of the cache lines they touch, z_t comes as a broadcast (every lane of a stage reads the same address), and the only
+// cross-lane step is the wave_sum the kernels take anyway. Any m in 1..64, T m below or above 64 (the row loop strides 64).
+template <typename real>
+struct RowsAuxArgs : XboxAuxArgs<real> {
+    const real *G, *h;
+    int m;
+    long sb_g, st_g;
+    long sb_h, st_h;
+};
+
+template <typename real, bool XB>
+__global__ __launch_bounds__(64) void k_merit_rows(RowsAuxArgs<real> a) {
+    const int lane = threadIdx.x;
+    const int b = blockIdx.x % a.B, kk = blockIdx.x / a.B;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, m = a.m;
+    const real *z = a.zc + ((size_t)kk * a.B + b) * T * n;
+    const real *xn = a.xnext + ((size_t)kk * a.B + b) * (T - 1) * nx;
+    const int xr = XB ? 2 * nx : 0, nit = 2 * nu + xr + m;   // inequality rows per stage
+    const real *lam = a.lam + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *Qd = a.Qd + (size_t)b * T * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = XB ? a.xlo + (size_t)b * a.sb_x : nullptr, *xhi = XB ? a.xhi + (size_t)b * a.sb_x : nullptr;
+    const real *Gb = a.G + (size_t)b * a.sb_g, *hb = a.h + (size_t)b * a.sb_h;
+    const real rho = a.rho[b];
+    real acc = 0, sq = 0;
+    for (int e = lane; e < T * n; e += 64) {
+        int t = e / n, j = e - t * n;
+        real v = z[e];
+        acc += (real(0.5) * Qd[e] * v + q[e]) * v;
+        const bool isu = j >= nx;
+        if (XB || isu) {
+            const int jj = isu ? j - nx : j, w = isu ? nu : nx;
+            real bh, bl;
+            if constexpr (XB) {
+                bh = isu ? uhi[t * a.st_u + jj] : xhi[t * a.st_x + jj];
+                bl = isu ? ulo[t * a.st_u + jj] : xlo[t * a.st_x + jj];
+            } else {
+                bh = uhi[t * a.st_u + jj];
+                bl = ulo[t * a.st_u + jj];
+            }
+            real vu = v - bh, vl = -v + bl;
+            real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+            int ru = neq + t * nit + (isu ? 0 : 2 * nu) + jj;
+            acc += lam[ru] * vu + lam[ru + w] * vl;
+            sq += cu * cu + cl * cl;
+        }
+    }
+    for (int e = lane; e < neq; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        acc += lam[e] * r;
+        sq += r * r;
+    }
+    // general rows: a lane per row
+    for (int e = lane; e < T * m; e += 64) {
+        const int t = e / m, k = e - t * m;
+        const real *g = Gb + (size_t)t * a.st_g + (size_t)k * n, *zt = z + t * n;
+        real s = 0;
+        for (int j = 0; j < n; ++j) s += g[j] * zt[j];
+        const real r = s - hb[(size_t)t * a.st_h + k], p = r > 0 ? r : real(0);
+        acc += lam[neq + t * nit + 2 * nu + xr + k] * r;
+        sq += p * p;
+    }
+    acc = wave_sum(acc);
+    sq = wave_sum(sq);
+    if (lane == 0) {
+        a.phi[(size_t)kk * a.B + b] = acc + real(0.5) * rho * sq;
+        if (a.rnorm2) a.rnorm2[(size_t)kk * a.B + b] = sq;
+    }
+}
+
+// k_merit_pick with the rows. A row is affine in the step length: one pass over G_k gives r0 = G_k . z_t - h_k and
+// gd = G_k . d_t, and the 20 candidates r0 + alpha gd come from registers like the box rows' candidates.
+template <typename real, bool XB>
+__global__ __launch_bounds__(64) void k_merit_pick_rows(RowsAuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, m = a.m;
+    const int xr = XB ? 2 * nx : 0, nit = 2 * nu + xr + m;
+    real *z = a.z + (size_t)b * T * n;
+    const real *d = a.d + (size_t)b * T * n;
+    const real *lam = a.lam + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *Qd = a.Qd + (size_t)b * T * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = XB ? a.xlo + (size_t)b * a.sb_x : nullptr, *xhi = XB ? a.xhi + (size_t)b * a.sb_x : nullptr;
+    const real *Gb = a.G + (size_t)b * a.sb_g, *hb = a.h + (size_t)b * a.sb_h;
+    const real rho = a.rho[b];
+    real acc[20], sq[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) { acc[k] = 0; sq[k] = 0; }
+    // cost + box rows (controls, and states when XB): every lane walks its elements once, all candidates from registers
+    for (int e = lane; e < T * n; e += 64) {
+        const int t = e / n, j = e - t * n;
+        const real zv = z[e], dv = d[e], Qv = Qd[e], qv = q[e];
+        real bu = 0, bl = 0, lu = 0, ll = 0;
+        const bool isu = j >= nx;
+        const bool has = XB || isu;
+        if (has) {
+            const int jj = isu ? j - nx : j, w = isu ? nu : nx;
+            const int ru = neq + t * nit + (isu ? 0 : 2 * nu) + jj;
+            if constexpr (XB) {
+                bu = isu ? uhi[t * a.st_u + jj] : xhi[t * a.st_x + jj];
+                bl = isu ? ulo[t * a.st_u + jj] : xlo[t * a.st_x + jj];
+            } else {
+                bu = uhi[t * a.st_u + jj];
+                bl = ulo[t * a.st_u + jj];
+            }
+            lu = lam[ru]; ll = lam[ru + w];
+        }
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            const real v = zv + alpha * dv;
+            acc[k] += (real(0.5) * Qv * v + qv) * v;
+            if (has) {
+                const real vu = v - bu, vl = -v + bl;
+                const real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+                acc[k] += lu * vu + ll * vl;
+                sq[k] += cu * cu + cl * cl;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    // equality rows: r = x_{t+1}(candidate) - xnext_k, init rows x_0 - x0
+    for (int e = lane; e < neq; e += 64) {
+        const int t = e / nx, i = e - t * nx;
+        const real le = lam[e];
+        const int zi = (t < T - 1) ? (t + 1) * n + i : i;
+        const real zv = z[zi], dv = d[zi];
+        const real x0v = (t < T - 1) ? real(0) : a.x0[(size_t)b * nx + i];
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            if (k < a.n_ls) {
+                const real ref = (t < T - 1) ? a.xnext[(((size_t)k * a.B + b) * (T - 1) + t) * nx + i] : x0v;
+                const real r = zv + alpha * dv - ref;
+                acc[k] += le * r;
+                sq[k] += r * r;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    // general rows: a lane per row, one pass over G_k for both dot products
+    for (int e = lane; e < T * m; e += 64) {
+        const int t = e / m, k = e - t * m;
+        const real *g = Gb + (size_t)t * a.st_g + (size_t)k * n, *zt = z + t * n, *dt = d + t * n;
+        real sz = 0, gd = 0;
+        for (int j = 0; j < n; ++j) {
+            const real gj = g[j];
+            sz += gj * zt[j];
+            gd += gj * dt[j];
+        }
+        const real r0 = sz - hb[(size_t)t * a.st_h + k];
+        const real lk = lam[neq + t * nit + 2 * nu + xr + k];
+        real alpha = 1;
+#pragma unroll
+        for (int c = 0; c < 20; ++c) {
+            const real r = r0 + alpha * gd, p = r > 0 ? r : real(0);
+            acc[c] += lk * r;
+            sq[c] += p * p;
+            alpha *= real(0.5);
+        }
+    }
+    int kbest = 0;
+    real best = 0, sqbest = 0;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) {
+        if (k < a.n_ls) {
+            const real s2 = wave_sum(sq[k]);
+            const real v = wave_sum(acc[k]) + real(0.5) * rho * s2;
+            if (a.phi) a.phi[(size_t)k * a.B + b] = v;     // (all lanes hold the same value)
+            if (k == 0) { best = v; sqbest = s2; }
+            else if (!(best != best) && (v != v || v < best)) { best = v; kbest = k; sqbest = s2; }
+        }
+    }
+    const real prev = a.phi_prev[b];
+    const bool ok = best < prev;
+    if (ok) {
+        const real alpha = real(1) / real(1 << kbest);
+        for (int e = lane; e < T * n; e += 64) z[e] += alpha * d[e];
+    }
+    if (lane == 0) {
+        a.phi_prev[b] = best;
+        if (a.k_out) a.k_out[b] = kbest;
+        if (a.accept_out) a.accept_out[b] = ok ? 1 : 0;
+        if (a.rnorm2 && ok) a.rnorm2[b] = sqbest;
+    }
+}
+
+template <typename real, bool XB>
+__global__ __launch_bounds__(64) void k_dual_rows(RowsAuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, m = a.m;
+    const real *z = a.zc + (size_t)b * T * n;
+    const real *xn = a.xnext + (size_t)b * (T - 1) * nx;
+    const int xr = XB ? 2 * nx : 0, nit = 2 * nu + xr + m;
+    real *lam = a.lam_io + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *Gb = a.G + (size_t)b * a.sb_g, *hb = a.h + (size_t)b * a.sb_h;
+    const real rho = a.rho_io[b];
+    for (int e = lane; e < neq; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        lam[e] += rho * r;
+    }
+    for (int e = lane; e < T * nu; e += 64) {
+        int t = e / nu, j = e - t * nu;
+        real u = z[t * n + nx + j];
+        int ru = neq + t * nit + j, rl = ru + nu;
+        real v1 = lam[ru] + rho * (u - uhi[t * a.st_u + j]);
+        real v2 = lam[rl] + rho * (-u + ulo[t * a.st_u + j]);
+        lam[ru] = v1 < 0 ? real(0) : v1;
+        lam[rl] = v2 < 0 ? real(0) : v2;
+    }
+    if constexpr (XB) {
+        const real *xlo = a.xlo + (size_t)b * a.sb_x, *xhi = a.xhi + (size_t)b * a.sb_x;
+        for (int e = lane; e < T * nx; e += 64) {
+            int t = e / nx, i = e - t * nx;
+            real x = z[t * n + i];
+            int ru = neq + t * nit + 2 * nu + i, rl = ru + nx;
+            real v1 = lam[ru] + rho * (x - xhi[t * a.st_x + i]);
+            real v2 = lam[rl] + rho * (-x + xlo[t * a.st_x + i]);
+            lam[ru] = v1 < 0 ? real(0) : v1;
+            lam[rl] = v2 < 0 ? real(0) : v2;
+        }
+    }
+    for (int e = lane; e < T * m; e += 64) {
+        const int t = e / m, k = e - t * m;
+        const real *g = Gb + (size_t)t * a.st_g + (size_t)k * n, *zt = z + t * n;
+        real s = 0;
+        for (int j = 0; j < n; ++j) s += g[j] * zt[j];
+        const int row = neq + t * nit + 2 * nu + xr + k;
+        const real v = lam[row] + rho * (s - hb[(size_t)t * a.st_h + k]);
+        lam[row] = v < 0 ? real(0) : v;
+    }
+    __syncthreads();
+    if (lane == 0) a.rho_io[b] = rho * a.rho_scale;
+}
+
+// what the three entry points below fill alike; false: ALQP_E_BADARG. x_lo and x_hi both null: no state bounds.
+template <typename real>
+bool set_rows_aux(const AlqpDims *dims, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                  const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,
+                  long sb_g, long st_g, long sb_h, long st_h, RowsAuxArgs<real> &a) {
+    if (!dims_ok(dims) || !x0 || !u_lo || !u_hi || !x_lo != !x_hi || sb_x < 0 || st_x < 0) return false;
+    if (!G || !h || m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) return false;
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu;
+    a.x0 = (const real *)x0;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
+    a.G = (const real *)G; a.h = (const real *)h; a.m = m;
+    a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
+    return true;
+}
+
+template <typename real>
+int merit_rows_impl(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                    const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                    const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                    long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                    void *phi, void *rnorm2, void *stream) {
+    RowsAuxArgs<real> a = {};
+    if (!set_rows_aux<real>(dims, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h,
+                            a) || K < 1 || !zc || !xnext || !lam || !rho || !Qd || !q || !phi)
+        return ALQP_E_BADARG;
+    a.K = K;
+    a.zc = (const real *)zc; a.xnext = (const real *)xnext;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.phi = (real *)phi; a.rnorm2 = (real *)rnorm2;
+    const dim3 grid((unsigned)((size_t)K * dims->B));
+    if (x_lo) hipLaunchKernelGGL((k_merit_rows<real, true>), grid, dim3(64), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_merit_rows<real, false>), grid, dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int merit_pick_rows_impl(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                         const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                         const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                         long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                         void *z, void *phi_prev, void *rnorm2, void *phi_all, int *k_out, int *accept_out,
+                         void *stream) {
+    RowsAuxArgs<real> a = {};
+    if (!set_rows_aux<real>(dims, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h,
+                            a) || n_ls < 1 || n_ls > 20 || !d || !xnext_all || !lam || !rho || !Qd || !q || !z ||
+        !phi_prev)
+        return ALQP_E_BADARG;
+    a.n_ls = n_ls;
+    a.d = (const real *)d; a.xnext = (const real *)xnext_all;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
+    a.z = (real *)z; a.phi_prev = (real *)phi_prev; a.rnorm2 = (real *)rnorm2; a.phi = (real *)phi_all;
+    a.k_out = k_out; a.accept_out = accept_out;
+    if (x_lo) hipLaunchKernelGGL((k_merit_pick_rows<real, true>), dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_merit_pick_rows<real, false>), dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int dual_rows_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *x0, const void *u_lo,
+                   const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                   const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h, void *lam,
+                   void *rho, double rho_scale, void *stream) {
+    RowsAuxArgs<real> a = {};
+    if (!set_rows_aux<real>(dims, x0, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h,
+                            a) || !z || !xnext || !lam || !rho)
+        return ALQP_E_BADARG;
+    a.zc = (const real *)z; a.xnext = (const real *)xnext;
+    a.lam_io = (real *)lam; a.rho_io = (real *)rho; a.rho_scale = (real)rho_scale;
+    if (x_lo) hipLaunchKernelGGL((k_dual_rows<real, true>), dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_dual_rows<real, false>), dim3(dims->B), dim3(64), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
 }  // namespace alqp
 
 extern "C" {
@@ -646,5 +971,39 @@ int alqp_exit_test(const double *sumsq, double *ctl, int mode, double tol, void 
 
 ALQP_DEFINE_AUX(f32, float)
 ALQP_DEFINE_AUX(f64, double)
+
+// the _rows twins: the _xbox arguments, then G, h, m and the four strides right behind the state-bound arguments
+#define ALQP_ROWS_PARAMS                                                                              \
+    const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,    \
+    long sb_g, long st_g, long sb_h, long st_h
+#define ALQP_ROWS_ARGS x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h
+#define ALQP_DEFINE_AUX_ROWS(SFX, REAL)                                                               \
+    int alqp_merit_rows_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,         \
+                              const void *x0, const void *lam, const void *rho, const void *Qd,       \
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u,           \
+                              long st_u, ALQP_ROWS_PARAMS, void *phi, void *rnorm2, void *stream) {   \
+        return alqp::merit_rows_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, \
+                                           st_u, ALQP_ROWS_ARGS, phi, rnorm2, stream);                \
+    }                                                                                                 \
+    int alqp_merit_pick_rows_##SFX(const AlqpDims *dims, int n_ls, const void *d,                     \
+                                   const void *xnext_all, const void *x0, const void *lam,            \
+                                   const void *rho, const void *Qd, const void *q, const void *u_lo,  \
+                                   const void *u_hi, long sb_u, long st_u, ALQP_ROWS_PARAMS, void *z, \
+                                   void *phi_prev, void *rnorm2, void *phi_all, int *k_out,           \
+                                   int *accept_out, void *stream) {                                   \
+        return alqp::merit_pick_rows_impl<REAL>(dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, u_lo,  \
+                                                u_hi, sb_u, st_u, ALQP_ROWS_ARGS, z, phi_prev,        \
+                                                rnorm2, phi_all, k_out, accept_out, stream);          \
+    }                                                                                                 \
+    int alqp_dual_update_rows_##SFX(const AlqpDims *dims, const void *z, const void *xnext,           \
+                                    const void *x0, const void *u_lo, const void *u_hi, long sb_u,    \
+                                    long st_u, ALQP_ROWS_PARAMS, void *lam, void *rho,                \
+                                    double rho_scale, void *stream) {                                 \
+        return alqp::dual_rows_impl<REAL>(dims, z, xnext, x0, u_lo, u_hi, sb_u, st_u, ALQP_ROWS_ARGS, \
+                                          lam, rho, rho_scale, stream);                               \
+    }
+
+ALQP_DEFINE_AUX_ROWS(f32, float)
+ALQP_DEFINE_AUX_ROWS(f64, double)
 
 }  // extern "C"

@@ -76,6 +76,8 @@ int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const Trac
 template <typename real>
 int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream);   // the state-bound unit
 template <typename real>
+int dispatch_step_rows(int nx, int nu, const RowsStepArgs<real> &a, hipStream_t stream);   // the row-step unit; XBOX iff a.xlo
+template <typename real>
 int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>
 int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);

@@ -170,18 +170,26 @@ class _Launcher:
                                     **self._out, **kw)
 
     # The PyTorch-dynamics route's four launches. With state bounds (xbnd) each goes to its _xbox twin, which takes xbnd
-    # behind the control bounds and knows no obstacle rows (the guards of MPC._run keep those apart).
+    # behind the control bounds and knows no obstacle rows (the guards of MPC._run keep those apart). With general rows
+    # (poly) each goes to its _rows twin, which takes xbnd (None: no state bounds) and poly behind the control bounds.
     def merit(self, z, xn, **okw):
+        if self.poly is not None:
+            return self.be.merit_rows(self.dims, 1, z, xn, *self._problem, self.xbnd, self.poly, self.phi, self.rn2, **okw)
         if self.xbnd is not None:
             return self.be.merit_xbox(self.dims, 1, z, xn, *self._problem, self.xbnd, self.phi, self.rn2, **okw)
         self.be.merit(self.dims, 1, z, xn, *self._problem, self.phi, self.rn2, **okw)
 
     def newton_step(self, z, xn, F, **kw):
+        if self.poly is not None:
+            return self.be.newton_step_rows(self.dims, z, xn, F, *self._problem, self.xbnd, self.poly, self.d, **kw)
         if self.xbnd is not None:
             return self.be.newton_step_xbox(self.dims, z, xn, F, *self._problem, self.xbnd, self.d, **kw)
         self.be.newton_step(self.dims, z, xn, F, *self._problem, self.d, **kw)
 
     def merit_pick(self, xn_all, z, **okw):
+        if self.poly is not None:
+            return self.be.merit_pick_rows(self.dims, N_LS, self.d, xn_all, *self._problem, self.xbnd, self.poly, z,
+                                           self.phi, rnorm2=self.rn2, k_out=self.k, accept_out=self.acc, **okw)
         if self.xbnd is not None:
             return self.be.merit_pick_xbox(self.dims, N_LS, self.d, xn_all, *self._problem, self.xbnd, z, self.phi,
                                            rnorm2=self.rn2, k_out=self.k, accept_out=self.acc, **okw)
@@ -190,6 +198,9 @@ class _Launcher:
 
     def dual_update(self, xn, **okw):
         st = self.st
+        if self.poly is not None:
+            return self.be.dual_update_rows(self.dims, st.z, xn, *self._x0_bounds, self.xbnd, self.poly, st.lam, st.rho,
+                                            RHO_SCALE, **okw)
         if self.xbnd is not None:
             return self.be.dual_update_xbox(self.dims, st.z, xn, *self._x0_bounds, self.xbnd, st.lam, st.rho, RHO_SCALE,
                                             **okw)
@@ -336,15 +347,21 @@ class MPC(Module):
     direction comes from the team kernel at any batch, and a provider with a compiled-in model (``PendulumDynamics``,
     ...) takes this route too. A backend without ``newton_step_xbox`` raises ``NotImplementedError`` for a callable
     ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``, and on the callable route not with
-    ``diag_cost=False`` or ``ineqG``. The gradients of the route in use stay available (callable ``dx``: ``q`` and
+    ``diag_cost=False``; with ``ineqG`` see below. The gradients of the route in use stay available (callable ``dx``: ``q`` and
     ``diag(C)``), taken with the active set held fixed.
 
     ``ineqG`` / ``ineqh`` (both or neither): m >= 1 general linear rows G_t tau_t <= h_t per stage, on all
     T stages next to the control bounds. ``ineqG`` is [m,n], [T,m,n] or [B,T,m,n], ``ineqh`` [m], [T,m] or [B,T,m]
     (independently); a non-finite ``ineqh`` entry means "no row". The reference carries the two arguments, but the code
     that reads them is never called (AL_mpc.py:496-498). ``lamda_prev`` is then [B, T nx + T (2 nu + m)]: the equality
-    rows, then per stage [u - u_upper | -u + u_lower | G_t tau_t - h_t]. LinDx routes only, like the state bounds. The
-    gradients above stay available, and the solve is also differentiable w.r.t. ``ineqh`` (active set held fixed); an
+    rows, then per stage [u - u_upper | -u + u_lower | G_t tau_t - h_t]. With ``LinDx`` the fused team kernel runs, at
+    any batch. With a callable ``dx`` / ``dx_jac`` the PyTorch-dynamics route runs with the row twins
+    of its four kernels (``HipBackend.newton_step_rows``, ``merit_rows``, ``merit_pick_rows``, ``dual_update_rows``),
+    which take the state bounds too when both are given: the direction comes from the team kernel at any batch, a
+    provider with a compiled-in model takes this route, and a backend without ``newton_step_rows`` raises
+    ``NotImplementedError`` for a callable ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``,
+    and on the callable route not with ``diag_cost=False``. The
+    gradients above stay available (callable ``dx``: ``q`` and ``diag(C)``), and the solve is also differentiable w.r.t. ``ineqh`` (active set held fixed); an
     ``ineqG`` that requires grad raises ``NotImplementedError``.
 
     ``diag_cost=False``, ``x_lower`` / ``x_upper`` and ``ineqG`` / ``ineqh`` go together, any two or all three (DESIGN
@@ -386,7 +403,8 @@ class MPC(Module):
             if not diag_cost and no_gen:
                 raise NotImplementedError(_NO_DENSE_XBOX)
         if ineqG is not None or ineqh is not None:
-            # the general rows live in the fused team kernel of the LinDx routes alone (alqp_solve_lin_poly)
+            # the general rows live in the fused team kernel of the LinDx routes (alqp_solve_lin_poly) and in the _rows
+            # twins of the launch-per-step kernels (a callable dx), which have no state-estimator row set
             if not diag_cost and no_gen:   # (before anything is asked of ineqG's shape or of ineqh)
                 raise NotImplementedError(_NO_DENSE_POLY)
             if ineqG is None or ineqh is None:
@@ -831,11 +849,12 @@ class MPC(Module):
 
     def _fused_model(self, st):
         """True when the dynamics model is compiled into the library (dynamics.py) and this solve may take it: plain
-        row set (the compiled-in models know no state-bound rows: with x_lower / x_upper a provider such as
-        PendulumDynamics takes the PyTorch-dynamics route), one call per solve (not the stream loop), the sizes it was
+        row set (the compiled-in models know no state-bound rows and no general rows: with x_lower / x_upper or
+        ineqG / ineqh a provider such as PendulumDynamics takes the PyTorch-dynamics route), one call per solve (not the stream loop), the sizes it was
         compiled for, and the model's default route unless `prefer_fused`."""
         dx = st.dx
         return (st.lin is None and not st.stream_mode and not self._has_extra_rows() and self.x_lower is None
+                and self.ineqG is None
                 and getattr(dx, "fused_id", None) is not None
                 and (getattr(dx, "fused_default", True) or self.prefer_fused)
                 and (getattr(dx, "nx", None), getattr(dx, "nu", None)) == (self.n_state, self.n_ctrl))
@@ -870,10 +889,11 @@ class MPC(Module):
         alphas = (2.0 ** -torch.arange(N_LS, device=z.device, dtype=z.dtype)).view(N_LS, 1, 1, 1)
         # from B = QUAD_MIN_BATCH on the direction comes from the quad kernels (obstacle rows / the state-estimator
         # row set included), whose factor stays in the workspace records: the private one when backward follows
-        # With state bounds the direction comes from the team kernel at any batch (no quad step kernel knows those rows):
-        # no workspace is fetched, and the packed factor is the saved one.
+        # With state bounds or general rows the direction comes from the team kernel at any batch (no quad step kernel
+        # knows those rows): no workspace is fetched, and the packed factor is the saved one.
         qws = L.qws   # (fetched once per solve, on the assumption L.lin_tracked states)
-        if qws is None and L.cached_ws is not None and L.dims[0] >= L.quad_min_batch and L.xbnd is None:
+        if (qws is None and L.cached_ws is not None and L.dims[0] >= L.quad_min_batch and L.xbnd is None
+                and L.poly is None):
             qws = L.cached_ws(L.dims, z)[0]
         steps = 0
         while steps < MAX_NEWTON:
@@ -1012,7 +1032,9 @@ class MPC(Module):
                 raise NotImplementedError(_NO_DENSE_XBOX)
             if self.ineqG is not None and not self.diag_cost:
                 raise NotImplementedError(_NO_DENSE_POLY)
-            if self.ineqG is not None and self.x_lower is not None:
+            # (with a callable dx the two together run on the _rows twins of the launch-per-step kernels alone)
+            if self.ineqG is not None and self.x_lower is not None and not (
+                    st.lin is None and hasattr(be, "newton_step_rows")):
                 raise NotImplementedError(_NO_XBOX_POLY)
         if not self.diag_cost:
             # the dense cost lives in the fused team kernel alone (alqp_solve_lin_dense): everything that reaches the
@@ -1036,22 +1058,24 @@ class MPC(Module):
             if self.linearize_once:
                 raise NotImplementedError("MPC: x_lower / x_upper with linearize_once: the frozen-linearisation route "
                                           "is not built with state-bound rows")
-            if st.lin is None and not hasattr(be, "newton_step_xbox"):
+            if st.lin is None and not (hasattr(be, "newton_step_xbox")
+                                       or (self.ineqG is not None and hasattr(be, "newton_step_rows"))):
                 raise NotImplementedError("MPC: x_lower / x_upper need affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models know no state-bound rows")
             if st.lam.shape[1] != self.neq + self.nineq:
                 raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the state bounds need "
                                  f"{self.neq + self.nineq} = T nx + T (2 nu + 2 nx{' + m' if self.n_rows else ''})")
         if self.ineqG is not None:
-            # the general rows live in the fused team kernel alone (alqp_solve_lin_poly): the launch-per-step helper
-            # kernels, k_newton_step* and the compiled-in models know no such rows
+            # the general rows live in the fused team kernel (alqp_solve_lin_poly) and, for a callable dx, in the
+            # launch-per-step kernels' _rows twins; the quad step kernels, the obstacle /
+            # state-estimator row sets and the compiled-in models know no such rows
             if self._has_extra_rows():
                 raise NotImplementedError("MPC: ineqG / ineqh with obstacle rows (Obstacle_MPC): those run on the "
                                           "nonlinear-caller kernels, which know no general rows")
             if self.linearize_once:
                 raise NotImplementedError("MPC: ineqG / ineqh with linearize_once: the frozen-linearisation route "
                                           "evaluates merit and dual update with kernels that know no general rows")
-            if st.lin is None:
+            if st.lin is None and not hasattr(be, "newton_step_rows"):
                 raise NotImplementedError("MPC: ineqG / ineqh need affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models know no general rows")
             if st.lam.shape[1] != self.neq + self.nineq:

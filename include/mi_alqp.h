@@ -422,6 +422,69 @@ int alqp_dual_update_xbox_f64(const AlqpDims *dims, const void *z, const void *x
                               void *lam, void *rho, double rho_scale, void *stream);
 
 /*
+ * The same four with the general rows of alqp_solve_lin_poly_* (m rows G_t [x_t; u_t] <= h_t per stage, on all T stages),
+ * with or without the state box rows: general rows with a caller-evaluated nonlinear model. Each takes its _xbox twin's
+ * arguments, with G, h, m, sb_g, st_g, sb_h, st_h right behind the state-bound arguments: row k of stage t of instance b
+ * at G + b*sb_g + t*st_g + k*n, its right-hand side at h + b*sb_h + t*st_h + k ([m][n]: 0, 0; [T][m][n]: 0, m n;
+ * [B][T][m][n]: T m n, m n; read in place), all finite. x_lo and x_hi may BOTH be null: no state bounds.
+ *   lam [B][T*nx + T*(2nu + XR + m)], XR = 2nx with state bounds and 0 without: per stage
+ *   [u - u_hi | -u + u_lo | (x - x_hi | -x + x_lo) | G_t z_t - h_t] behind the equality rows.
+ * A row follows the box rows' conventions: lam_k r_k with the unclamped r_k = G_k . z_t - h_k plus rho/2 max(r_k, 0)^2 in
+ * the merit, max(r_k, 0)^2 in rnorm2, rho G_k' G_k in H_tt while r_k >= 0, max(0, lam_k + rho r_k) in the dual update.
+ * alqp_newton_step_rows_*: the team kernel only - no workspace argument; the packed factor_out is what alqp_backward_*
+ * takes. ALQP_E_UNSUPPORTED for an (nx, nu) that is not compiled and for a horizon or m whose LDS image (the team image plus
+ * 2 pad4(m) words per team) does not fit; ALQP_E_BADARG for a null G or h, m outside 1..64, one of x_lo / x_hi null alone,
+ * a negative stride, an empty batch, and for n_ls outside 1..20 in alqp_merit_pick_rows_*.
+ * ADDED under ABI version 17 like the _xbox symbols: detect them by symbol lookup.
+ */
+int alqp_newton_step_rows_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
+                              const void *x0, const void *lam, const void *rho, const void *Qd,
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                              void *d_out, void *g_out, void *factor_out, int *info, void *stream);
+int alqp_newton_step_rows_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
+                              const void *x0, const void *lam, const void *rho, const void *Qd,
+                              const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                              void *d_out, void *g_out, void *factor_out, int *info, void *stream);
+int alqp_merit_rows_f32(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                        const void *lam, const void *rho, const void *Qd, const void *q,
+                        const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                        const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                        const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                        void *phi, void *rnorm2, void *stream);
+int alqp_merit_rows_f64(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                        const void *lam, const void *rho, const void *Qd, const void *q,
+                        const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                        const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                        const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                        void *phi, void *rnorm2, void *stream);
+int alqp_merit_pick_rows_f32(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                             const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                             const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                             long sb_x, long st_x, const void *G, const void *h, int m, long sb_g, long st_g,
+                             long sb_h, long st_h, void *z, void *phi_prev, void *rnorm2, void *phi_all,
+                             int *k_out, int *accept_out, void *stream);
+int alqp_merit_pick_rows_f64(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                             const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
+                             const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                             long sb_x, long st_x, const void *G, const void *h, int m, long sb_g, long st_g,
+                             long sb_h, long st_h, void *z, void *phi_prev, void *rnorm2, void *phi_all,
+                             int *k_out, int *accept_out, void *stream);
+int alqp_dual_update_rows_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
+                              const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                              void *lam, void *rho, double rho_scale, void *stream);
+int alqp_dual_update_rows_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *x0,
+                              const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                              const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                              const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                              void *lam, void *rho, double rho_scale, void *stream);
+
+/*
  * Backward of the implicit layer (NewtonAL.backward, al_utils.py:578-615):
  * w = -H^{-1} gbar with the saved factor; q_grad = w, Qd_grad = w * z_final.
  * rho is the penalty the factor was built with. Exactly one of `factor` and `workspace` is non-null:
