@@ -130,6 +130,14 @@ _SIGS = {
                                        _P, _P, _P, _P, _P, _P, _P]),
     "alqp_dual_update_rows": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, C.c_long, C.c_long,
                                         _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, C.c_double, _P]),
+    # step, merit and pick with a dense stage cost: the _rows signatures, C where Qd stood (G, h null with m = 0: no rows)
+    "alqp_newton_step_dense": (C.c_int, [C.POINTER(AlqpDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                         C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, _P, _P, _P]),
+    "alqp_merit_dense": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, _P]),
+    "alqp_merit_pick_dense": (C.c_int, [C.POINTER(AlqpDims), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS,
+                                        _P, _P, _P, _P, _P, _P, _P]),
     "alqp_ipm_solve": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpIpmParams), _P, _P, _P, _P, _P, _P, _P,
                                  C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _P, C.c_size_t, _P,
                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -787,6 +787,72 @@ class HipBackend:
             _stream())
         _lib.check(rc, "alqp_dual_update_rows_" + sfx)
 
+    # -- step, merit and pick with a dense stage cost, with or without state box rows and general rows (alqp_*_dense):
+    # MPC(diag_cost=False) with a callable dx. The dual update reads no cost: dual_update, _xbox or _rows ---------------
+    def _dense_cargs(self, dims, lam, Cs, xbnd, poly, dt):
+        """solve_lin_dense's check on Cs with _xbox_checks / _rows_checks on the rows -> the C arguments from x_lo to st_h."""
+        B, T, nx, nu = dims
+        n = nx + nu
+        if tuple(Cs.shape) != (B, T, n, n):
+            raise ValueError(f"mi_alqp: C has shape {tuple(Cs.shape)}, expected {(B, T, n, n)}")
+        if poly is not None:
+            return self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
+        if xbnd is not None:
+            return self._rows_cargs((*self._xbox_checks(dims, lam, xbnd), None, None, 0, 0, 0, 0, 0), dt)
+        M = T * nx + 2 * T * nu
+        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
+            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, expected [B, {M}]")
+        return (None, None, 0, 0, None, None, 0, 0, 0, 0, 0)
+
+    def newton_step_dense(self, dims, z, xnext, F, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out,
+                          g_out=None, factor=None, info=None):
+        """newton_step with a dense stage cost (alqp_newton_step_dense): Cs [B,T,n,n], symmetric, in place of Qd;
+        xbnd = (xlo, xhi, sb_x, st_x) or None, poly = (G, h, m, sb_g, st_g, sb_h, st_h) or None,
+        lam [B, T nx + T (2 nu + [2 nx] + [m])]. The team kernel at any batch (no workspace), optional packed `factor`."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        rows = self._dense_cargs(dims, lam, Cs, xbnd, poly, dt)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_newton_step_dense_" + sfx)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Cs, "C", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(d_out, "d_out", dt),
+            _ptr(g_out, "g_out", dt, True), _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True),
+            _stream())
+        _lib.check(rc, "alqp_newton_step_dense_" + sfx)
+        self.last_step_kernel = "k_newton_step_dense"
+
+    def merit_dense(self, dims, K, zc, xnext, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2=None):
+        """merit with a dense stage cost (alqp_merit_dense); Cs, xbnd, poly and lam as newton_step_dense."""
+        B, T, nx, nu = dims
+        dt = zc.dtype
+        sfx = _dt(zc)
+        rows = self._dense_cargs(dims, lam, Cs, xbnd, poly, dt)
+        d = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_merit_dense_" + sfx)(
+            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Cs, "C", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(phi, "phi", dt),
+            _ptr(rnorm2, "rnorm2", dt, True), _stream())
+        _lib.check(rc, "alqp_merit_dense_" + sfx)
+
+    def merit_pick_dense(self, dims, n_ls, d, xnext_all, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
+                         phi_prev, rnorm2=None, phi_all=None, k_out=None, accept_out=None):
+        """merit_pick with a dense stage cost (alqp_merit_pick_dense); Cs, xbnd, poly and lam as newton_step_dense."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        sfx = _dt(z)
+        rows = self._dense_cargs(dims, lam, Cs, xbnd, poly, dt)
+        dd = _lib.AlqpDims(B, T, nx, nu)
+        rc = getattr(self.lib, "alqp_merit_pick_dense_" + sfx)(
+            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Cs, "C", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(z, "z", dt),
+            _ptr(phi_prev, "phi_prev", dt), _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
+            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
+        _lib.check(rc, "alqp_merit_pick_dense_" + sfx)
+
     def _backward(self, dims, factor, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, dyn):
         """alqp_backward_*: `factor` or `workspace` is a device pointer, the other None."""
         dt = gbar.dtype

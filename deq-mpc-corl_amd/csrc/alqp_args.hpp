@@ -185,6 +185,24 @@ struct RowsStepArgs : XboxStepArgs<real> {
     long sb_h, st_h;
 };
 
+// The one-step kernel with a dense stage cost (k_newton_step_dense<.., XBOX, POLY>): RowsStepArgs with C where Qd stood and
+// without the obstacle fields, a type of its own. The state bounds are read only by the XBOX instantiations, the rows only
+// by the POLY ones (null / m = 0 otherwise).
+template <typename real>
+struct DenseStepArgs {
+    int B, T;
+    const real *z, *xnext, *F, *x0, *lam, *rho, *C, *q, *ulo, *uhi;   // C: [B][T][n][n] row-major, symmetric
+    long sb_u, st_u;
+    const real *xlo, *xhi;
+    long sb_x, st_x;
+    const real *G, *h;
+    int m;
+    long sb_g, st_g;
+    long sb_h, st_h;
+    real *d_out, *g_out, *factor;
+    int *info;
+};
+
 // DYN = false: the plain backward (alqp_backward_* with dyn = NULL), the kernel arguments it always had. DYN = true (a
 // non-null AlqpBwdDyn) adds the gradients w.r.t. the affine dynamics and the initial state behind them, in a type of
 // its own so that the plain kernels' argument block, and with it their code, stays what it was.

@@ -1,6 +1,6 @@
 // alqp_aux.hip - the size-generic helper kernels of the launch-per-step routes (merit, line-search pick, dual update,
 // batch-global exit test; one wavefront per instance) with their C ABI, and the state-bound twins of merit, pick and dual,
-// and their twins with general rows (with or without state bounds).
+// and their twins with general rows (with or without state bounds), and merit and pick with a dense stage cost.
 #include <hip/hip_runtime.h>
 
 #include "alqp_launch.hpp"   // dims_ok, set_obstacles
@@ -901,6 +901,293 @@ int dual_rows_impl(const AlqpDims *dims, const void *z, const void *xnext, const
     return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
 }
 
+// ---- merit and pick with a dense stage cost 1/2 z_t' C_t z_t + q_t' z_t (MPC(diag_cost=False) with a callable dx), alone or
+// with state box rows (XB) and / or general rows (PL) ----------------------------------------------------------------------
+// Kernels and an argument type of their own once more: RowsAuxArgs with C ([B][T][n][n] row-major, symmetric) where Qd stood.
+// Multipliers per stage [u - uhi | -u + ulo | (x - xhi | -x + xlo) | (G_t z_t - h_t)], stage stride 2 nu + XR + (PL ? m : 0);
+// the constraint terms are the _rows twins' statements. The dual update reads no cost and has no twin here.
+// The cost term, a lane per element: element e = t n + i (lane e mod 64) reads row i of C_t once, n consecutive words, and
+// forms (C_t z_t)_i in the order j = 0 .. n-1 with z_t as a broadcast; 64 lanes cover consecutive rows, so every byte of the
+// lines they touch is used, and the sum's order does not depend on a lane split (the lane-per-row reasoning of the rows above).
+template <typename real>
+struct DenseAuxArgs {
+    int B, T, nx, nu, K, n_ls;
+    const real *zc, *xnext, *x0, *lam, *rho, *C, *q, *ulo, *uhi;
+    long sb_u, st_u;
+    const real *xlo, *xhi;
+    long sb_x, st_x;
+    const real *G, *h;
+    int m;
+    long sb_g, st_g;
+    long sb_h, st_h;
+    real *phi, *rnorm2;
+    // pick
+    const real *d;
+    real *phi_prev, *z;
+    int *k_out, *accept_out;
+};
+
+template <typename real, bool XB, bool PL>
+__global__ __launch_bounds__(64) void k_merit_dense(DenseAuxArgs<real> a) {
+    const int lane = threadIdx.x;
+    const int b = blockIdx.x % a.B, kk = blockIdx.x / a.B;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, m = PL ? a.m : 0;
+    const real *z = a.zc + ((size_t)kk * a.B + b) * T * n;
+    const real *xn = a.xnext + ((size_t)kk * a.B + b) * (T - 1) * nx;
+    const int xr = XB ? 2 * nx : 0, nit = 2 * nu + xr + m;   // inequality rows per stage
+    const real *lam = a.lam + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *Cb = a.C + (size_t)b * T * n * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = XB ? a.xlo + (size_t)b * a.sb_x : nullptr, *xhi = XB ? a.xhi + (size_t)b * a.sb_x : nullptr;
+    const real rho = a.rho[b];
+    real acc = 0, sq = 0;
+    for (int e = lane; e < T * n; e += 64) {
+        int t = e / n, j = e - t * n;
+        real v = z[e];
+        // row j of C_t (C_t is the t-th n x n block: row e of the [T n][n] image) against z_t
+        const real *c = Cb + (size_t)e * n, *zt = z + t * n;
+        real cz = 0;
+        for (int i = 0; i < n; ++i) cz += c[i] * zt[i];
+        acc += (real(0.5) * cz + q[e]) * v;
+        const bool isu = j >= nx;
+        if (XB || isu) {
+            const int jj = isu ? j - nx : j, w = isu ? nu : nx;
+            real bh, bl;
+            if constexpr (XB) {
+                bh = isu ? uhi[t * a.st_u + jj] : xhi[t * a.st_x + jj];
+                bl = isu ? ulo[t * a.st_u + jj] : xlo[t * a.st_x + jj];
+            } else {
+                bh = uhi[t * a.st_u + jj];
+                bl = ulo[t * a.st_u + jj];
+            }
+            real vu = v - bh, vl = -v + bl;
+            real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+            int ru = neq + t * nit + (isu ? 0 : 2 * nu) + jj;
+            acc += lam[ru] * vu + lam[ru + w] * vl;
+            sq += cu * cu + cl * cl;
+        }
+    }
+    for (int e = lane; e < neq; e += 64) {
+        int t = e / nx, i = e - t * nx;
+        real r = (t < T - 1) ? z[(t + 1) * n + i] - xn[t * nx + i] : z[i] - a.x0[(size_t)b * nx + i];
+        acc += lam[e] * r;
+        sq += r * r;
+    }
+    if constexpr (PL) {   // general rows: a lane per row
+        const real *Gb = a.G + (size_t)b * a.sb_g, *hb = a.h + (size_t)b * a.sb_h;
+        for (int e = lane; e < T * m; e += 64) {
+            const int t = e / m, k = e - t * m;
+            const real *g = Gb + (size_t)t * a.st_g + (size_t)k * n, *zt = z + t * n;
+            real s = 0;
+            for (int j = 0; j < n; ++j) s += g[j] * zt[j];
+            const real r = s - hb[(size_t)t * a.st_h + k], p = r > 0 ? r : real(0);
+            acc += lam[neq + t * nit + 2 * nu + xr + k] * r;
+            sq += p * p;
+        }
+    }
+    acc = wave_sum(acc);
+    sq = wave_sum(sq);
+    if (lane == 0) {
+        a.phi[(size_t)kk * a.B + b] = acc + real(0.5) * rho * sq;
+        if (a.rnorm2) a.rnorm2[(size_t)kk * a.B + b] = sq;
+    }
+}
+
+// k_merit_pick with the dense cost. The cost is quadratic in the step length, and row i of C_t is read ONCE for all n_ls
+// candidates: one pass gives cz = C_t[i,:] . z_t and cd = C_t[i,:] . d_t, and candidate alpha is
+// (1/2 (cz + alpha cd) + q_i) (z_i + alpha d_i) from registers, like a general row's r0 + alpha gd. (n is a run-time number
+// in these size-generic kernels, so a row held in registers for a dot product per candidate would need an array of the
+// largest n and 20 n-long passes; two scalars cost two registers at any n.)
+template <typename real, bool XB, bool PL>
+__global__ __launch_bounds__(64) void k_merit_pick_dense(DenseAuxArgs<real> a) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int T = a.T, nx = a.nx, nu = a.nu, n = nx + nu, neq = T * nx, m = PL ? a.m : 0;
+    const int xr = XB ? 2 * nx : 0, nit = 2 * nu + xr + m;
+    real *z = a.z + (size_t)b * T * n;
+    const real *d = a.d + (size_t)b * T * n;
+    const real *lam = a.lam + (size_t)b * ((size_t)neq + (size_t)T * nit);
+    const real *Cb = a.C + (size_t)b * T * n * n, *q = a.q + (size_t)b * T * n;
+    const real *ulo = a.ulo + (size_t)b * a.sb_u, *uhi = a.uhi + (size_t)b * a.sb_u;
+    const real *xlo = XB ? a.xlo + (size_t)b * a.sb_x : nullptr, *xhi = XB ? a.xhi + (size_t)b * a.sb_x : nullptr;
+    const real rho = a.rho[b];
+    real acc[20], sq[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) { acc[k] = 0; sq[k] = 0; }
+    // cost + box rows (controls, and states when XB): every lane walks its elements once, all candidates from registers
+    for (int e = lane; e < T * n; e += 64) {
+        const int t = e / n, j = e - t * n;
+        const real zv = z[e], dv = d[e], qv = q[e];
+        const real *c = Cb + (size_t)e * n, *zt = z + t * n, *dt = d + t * n;
+        real cz = 0, cd = 0;
+        for (int i = 0; i < n; ++i) {
+            const real ci = c[i];
+            cz += ci * zt[i];
+            cd += ci * dt[i];
+        }
+        real bu = 0, bl = 0, lu = 0, ll = 0;
+        const bool isu = j >= nx;
+        const bool has = XB || isu;
+        if (has) {
+            const int jj = isu ? j - nx : j, w = isu ? nu : nx;
+            const int ru = neq + t * nit + (isu ? 0 : 2 * nu) + jj;
+            if constexpr (XB) {
+                bu = isu ? uhi[t * a.st_u + jj] : xhi[t * a.st_x + jj];
+                bl = isu ? ulo[t * a.st_u + jj] : xlo[t * a.st_x + jj];
+            } else {
+                bu = uhi[t * a.st_u + jj];
+                bl = ulo[t * a.st_u + jj];
+            }
+            lu = lam[ru]; ll = lam[ru + w];
+        }
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            const real v = zv + alpha * dv;
+            acc[k] += (real(0.5) * (cz + alpha * cd) + qv) * v;
+            if (has) {
+                const real vu = v - bu, vl = -v + bl;
+                const real cu = vu > 0 ? vu : real(0), cl = vl > 0 ? vl : real(0);
+                acc[k] += lu * vu + ll * vl;
+                sq[k] += cu * cu + cl * cl;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    // equality rows: r = x_{t+1}(candidate) - xnext_k, init rows x_0 - x0
+    for (int e = lane; e < neq; e += 64) {
+        const int t = e / nx, i = e - t * nx;
+        const real le = lam[e];
+        const int zi = (t < T - 1) ? (t + 1) * n + i : i;
+        const real zv = z[zi], dv = d[zi];
+        const real x0v = (t < T - 1) ? real(0) : a.x0[(size_t)b * nx + i];
+        real alpha = 1;
+#pragma unroll
+        for (int k = 0; k < 20; ++k) {
+            if (k < a.n_ls) {
+                const real ref = (t < T - 1) ? a.xnext[(((size_t)k * a.B + b) * (T - 1) + t) * nx + i] : x0v;
+                const real r = zv + alpha * dv - ref;
+                acc[k] += le * r;
+                sq[k] += r * r;
+            }
+            alpha *= real(0.5);
+        }
+    }
+    if constexpr (PL) {   // general rows: a lane per row, one pass over G_k for both dot products
+        const real *Gb = a.G + (size_t)b * a.sb_g, *hb = a.h + (size_t)b * a.sb_h;
+        for (int e = lane; e < T * m; e += 64) {
+            const int t = e / m, k = e - t * m;
+            const real *g = Gb + (size_t)t * a.st_g + (size_t)k * n, *zt = z + t * n, *dt = d + t * n;
+            real sz = 0, gd = 0;
+            for (int j = 0; j < n; ++j) {
+                const real gj = g[j];
+                sz += gj * zt[j];
+                gd += gj * dt[j];
+            }
+            const real r0 = sz - hb[(size_t)t * a.st_h + k];
+            const real lk = lam[neq + t * nit + 2 * nu + xr + k];
+            real alpha = 1;
+#pragma unroll
+            for (int c = 0; c < 20; ++c) {
+                const real r = r0 + alpha * gd, p = r > 0 ? r : real(0);
+                acc[c] += lk * r;
+                sq[c] += p * p;
+                alpha *= real(0.5);
+            }
+        }
+    }
+    int kbest = 0;
+    real best = 0, sqbest = 0;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) {
+        if (k < a.n_ls) {
+            const real s2 = wave_sum(sq[k]);
+            const real v = wave_sum(acc[k]) + real(0.5) * rho * s2;
+            if (a.phi) a.phi[(size_t)k * a.B + b] = v;     // (all lanes hold the same value)
+            if (k == 0) { best = v; sqbest = s2; }
+            else if (!(best != best) && (v != v || v < best)) { best = v; kbest = k; sqbest = s2; }
+        }
+    }
+    const real prev = a.phi_prev[b];
+    const bool ok = best < prev;
+    if (ok) {
+        const real alpha = real(1) / real(1 << kbest);
+        for (int e = lane; e < T * n; e += 64) z[e] += alpha * d[e];
+    }
+    if (lane == 0) {
+        a.phi_prev[b] = best;
+        if (a.k_out) a.k_out[b] = kbest;
+        if (a.accept_out) a.accept_out[b] = ok ? 1 : 0;
+        if (a.rnorm2 && ok) a.rnorm2[b] = sqbest;
+    }
+}
+
+// what the two entry points below fill alike; false: ALQP_E_BADARG. x_lo and x_hi both null: no state bounds; G and h both
+// null with m == 0: no general rows.
+template <typename real>
+bool set_dense_aux(const AlqpDims *dims, const void *x0, const void *C, const void *u_lo, const void *u_hi, long sb_u,
+                   long st_u, const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,
+                   long sb_g, long st_g, long sb_h, long st_h, DenseAuxArgs<real> &a) {
+    if (!dims_ok(dims) || !x0 || !C || !u_lo || !u_hi || !x_lo != !x_hi || sb_x < 0 || st_x < 0) return false;
+    if (!G != !h || (G ? (m < 1 || m > 64) : m != 0) || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) return false;
+    a.B = dims->B; a.T = dims->T; a.nx = dims->nx; a.nu = dims->nu;
+    a.x0 = (const real *)x0; a.C = (const real *)C;
+    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
+    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
+    a.G = (const real *)G; a.h = (const real *)h; a.m = m;
+    a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
+    return true;
+}
+
+// launches KERNEL<real, XB, PL> with XB = (x_lo != null), PL = (G != null)
+#define ALQP_LAUNCH_DENSE_AUX(KERNEL, GRID)                                                                          \
+    do {                                                                                                             \
+        if (x_lo && G) hipLaunchKernelGGL((KERNEL<real, true, true>), GRID, dim3(64), 0, (hipStream_t)stream, a);    \
+        else if (x_lo) hipLaunchKernelGGL((KERNEL<real, true, false>), GRID, dim3(64), 0, (hipStream_t)stream, a);   \
+        else if (G) hipLaunchKernelGGL((KERNEL<real, false, true>), GRID, dim3(64), 0, (hipStream_t)stream, a);      \
+        else hipLaunchKernelGGL((KERNEL<real, false, false>), GRID, dim3(64), 0, (hipStream_t)stream, a);            \
+    } while (0)
+
+template <typename real>
+int merit_dense_impl(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                     const void *lam, const void *rho, const void *C, const void *q, const void *u_lo,
+                     const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                     long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                     void *phi, void *rnorm2, void *stream) {
+    DenseAuxArgs<real> a = {};
+    if (!set_dense_aux<real>(dims, x0, C, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h,
+                             st_h, a) || K < 1 || !zc || !xnext || !lam || !rho || !q || !phi)
+        return ALQP_E_BADARG;
+    a.K = K;
+    a.zc = (const real *)zc; a.xnext = (const real *)xnext;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.q = (const real *)q;
+    a.phi = (real *)phi; a.rnorm2 = (real *)rnorm2;
+    const dim3 grid((unsigned)((size_t)K * dims->B));
+    ALQP_LAUNCH_DENSE_AUX(k_merit_dense, grid);
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+
+template <typename real>
+int merit_pick_dense_impl(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                          const void *lam, const void *rho, const void *C, const void *q, const void *u_lo,
+                          const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                          long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                          void *z, void *phi_prev, void *rnorm2, void *phi_all, int *k_out, int *accept_out,
+                          void *stream) {
+    DenseAuxArgs<real> a = {};
+    if (!set_dense_aux<real>(dims, x0, C, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h,
+                             st_h, a) || n_ls < 1 || n_ls > 20 || !d || !xnext_all || !lam || !rho || !q || !z ||
+        !phi_prev)
+        return ALQP_E_BADARG;
+    a.n_ls = n_ls;
+    a.d = (const real *)d; a.xnext = (const real *)xnext_all;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.q = (const real *)q;
+    a.z = (real *)z; a.phi_prev = (real *)phi_prev; a.rnorm2 = (real *)rnorm2; a.phi = (real *)phi_all;
+    a.k_out = k_out; a.accept_out = accept_out;
+    ALQP_LAUNCH_DENSE_AUX(k_merit_pick_dense, dim3(dims->B));
+    return hipGetLastError() == hipSuccess ? 0 : ALQP_E_LAUNCH;
+}
+#undef ALQP_LAUNCH_DENSE_AUX
+
 }  // namespace alqp
 
 extern "C" {
@@ -1005,5 +1292,28 @@ ALQP_DEFINE_AUX(f64, double)
 
 ALQP_DEFINE_AUX_ROWS(f32, float)
 ALQP_DEFINE_AUX_ROWS(f64, double)
+
+// the _dense twins of merit and pick: the _rows arguments with C where Qd stood (G, h null with m = 0: no general rows)
+#define ALQP_DEFINE_AUX_DENSE(SFX, REAL)                                                              \
+    int alqp_merit_dense_##SFX(const AlqpDims *dims, int K, const void *zc, const void *xnext,        \
+                               const void *x0, const void *lam, const void *rho, const void *C,       \
+                               const void *q, const void *u_lo, const void *u_hi, long sb_u,          \
+                               long st_u, ALQP_ROWS_PARAMS, void *phi, void *rnorm2, void *stream) {  \
+        return alqp::merit_dense_impl<REAL>(dims, K, zc, xnext, x0, lam, rho, C, q, u_lo, u_hi, sb_u, \
+                                            st_u, ALQP_ROWS_ARGS, phi, rnorm2, stream);               \
+    }                                                                                                 \
+    int alqp_merit_pick_dense_##SFX(const AlqpDims *dims, int n_ls, const void *d,                    \
+                                    const void *xnext_all, const void *x0, const void *lam,           \
+                                    const void *rho, const void *C, const void *q, const void *u_lo,  \
+                                    const void *u_hi, long sb_u, long st_u, ALQP_ROWS_PARAMS,         \
+                                    void *z, void *phi_prev, void *rnorm2, void *phi_all, int *k_out, \
+                                    int *accept_out, void *stream) {                                  \
+        return alqp::merit_pick_dense_impl<REAL>(dims, n_ls, d, xnext_all, x0, lam, rho, C, q, u_lo,  \
+                                                 u_hi, sb_u, st_u, ALQP_ROWS_ARGS, z, phi_prev,       \
+                                                 rnorm2, phi_all, k_out, accept_out, stream);         \
+    }
+
+ALQP_DEFINE_AUX_DENSE(f32, float)
+ALQP_DEFINE_AUX_DENSE(f64, double)
 
 }  // extern "C"

@@ -77,6 +77,9 @@ template <typename real>
 int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream);   // the state-bound unit
 template <typename real>
 int dispatch_step_rows(int nx, int nu, const RowsStepArgs<real> &a, hipStream_t stream);   // the row-step unit; XBOX iff a.xlo
+// the dense-step units, one object per POLY (alqp_team_dense_step, alqp_team_dense_step_rows); XBOX iff a.xlo
+template <typename real, bool POLY>
+int dispatch_step_dense(int nx, int nu, const DenseStepArgs<real> &a, hipStream_t stream);
 template <typename real>
 int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
 template <typename real>

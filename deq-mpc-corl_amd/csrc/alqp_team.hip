@@ -1,7 +1,7 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
 #if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT) || defined(ALQP_POLY_UNIT) || \
-    defined(ALQP_SHDYN_UNIT) || defined(ALQP_GEN_UNIT) || defined(ALQP_ROWS_STEP_UNIT)
+    defined(ALQP_SHDYN_UNIT) || defined(ALQP_GEN_UNIT) || defined(ALQP_ROWS_STEP_UNIT) || defined(ALQP_DENSE_STEP_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -46,6 +46,8 @@ __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/tea
 // builds only, and no spilling instantiation (tools/spill_report.py), for the reason given above.
 // The row-step unit (-DALQP_ROWS_STEP_UNIT) holds no fused solve: k_newton_step_rows below, the one-step kernel over
 // Team<.., XBOX, POLY> (general rows, with or without state bounds, with a callable dx). Uncapped builds only.
+// The dense-step units (-DALQP_DENSE_STEP_UNIT=<0|1>, the value is POLY; one object each) hold no fused solve either:
+// k_newton_step_dense below, the one-step kernel over Team<.., true, XBOX, POLY> (a full C_t with a callable dx).
 #if defined(ALQP_GEN_UNIT)
 template <typename real, int NX, int NU, bool DENSE, bool XBOX, bool POLY, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_gen(GenSolveArgs<real> a, TraceArgs<real> tr) {
@@ -440,6 +442,66 @@ __global__ __launch_bounds__(64, 1) void k_newton_step_rows(RowsStepArgs<real> a
 }
 #endif
 
+#ifdef ALQP_DENSE_STEP_UNIT
+// The same with a dense stage cost 1/2 z_t' C_t z_t + q_t' z_t (the dense-step units only), alone or with state box rows
+// (XBOX) and / or general rows (POLY): k_newton_step_rows' body over Team<.., true, XBOX, POLY>, C at a.C ([B][T][N][N]) and no
+// gQd. Multipliers per stage [u | (x) | (G)], M = T nx + T (2 nu + (XBOX ? 2 nx : 0) + (POLY ? m : 0)) per instance; with POLY
+// the LDS image grows by the hand-over region of 2 pad4(m) words per team. No obstacle rows and no state-estimator row set.
+template <typename real, int NX, int NU, bool XBOX, bool POLY>
+__global__ __launch_bounds__(64, 1) void k_newton_step_dense(DenseStepArgs<real> a) {
+    using C = Cfg<real, NX, NU>;
+    constexpr int G = C::G, N = C::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    real *smem = reinterpret_cast<real *>(smem_raw);
+    const int lane = threadIdx.x, team = lane / G, li = lane % G;
+    const int b_raw = blockIdx.x * C::QPW + team;
+    const bool active = b_raw < a.B;
+    const int b = active ? b_raw : a.B - 1;
+    const int T = a.T;
+    const size_t M = (size_t)C::M(T) + (XBOX ? (size_t)2 * T * NX : 0) + (POLY ? (size_t)T * a.m : 0);
+    const int team_words = C::team_words(T) + (POLY ? 2 * pad4(a.m) : 0);   // the team image, then the hand-over region
+
+    Team<real, NX, NU, true, XBOX, POLY> tm;
+    tm.init(smem + (size_t)team * team_words + opaque_zero(), li, team * G, T, b);
+    tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
+    tm.gq = a.q + (size_t)b * T * N;
+    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
+    tm.gc = nullptr;
+    tm.gx0 = a.x0 + (size_t)b * NX;
+    tm.gulo = a.ulo + (size_t)b * a.sb_u;
+    tm.guhi = a.uhi + (size_t)b * a.sb_u;
+    tm.st_u = a.st_u;
+    if constexpr (XBOX) {
+        tm.gxlo = a.xlo + (size_t)b * a.sb_x;
+        tm.gxhi = a.xhi + (size_t)b * a.sb_x;
+        tm.st_x = a.st_x;
+    }
+    if constexpr (POLY) {
+        tm.gG = a.G + (size_t)b * a.sb_g;
+        tm.gh = a.h + (size_t)b * a.sb_h;
+        tm.st_g = a.st_g; tm.st_h = a.st_h; tm.pm = a.m;
+        tm.ps = tm.Xp + pad4(T * C::XT);
+    }
+    tm.gxnext = a.xnext + (size_t)b * (T - 1) * NX;
+    const real *gz = a.z + (size_t)b * T * N;
+    tm.lams = const_cast<real *>(a.lam) + (size_t)b * M;  // read-only here
+    for (int e = li; e < T * N; e += G) tm.zs[e] = gz[e];
+    tm.rho = a.rho[b];
+    wave_sync();
+    tm.forward_sweep((active && a.g_out) ? a.g_out + (size_t)b * T * N : nullptr);
+    tm.backward_sweep();
+    if (active) {
+        real *gd = a.d_out + (size_t)b * T * N;
+        for (int e = li; e < T * N; e += G) gd[e] = tm.ds[e];
+        if (a.factor) {
+            real *gf = a.factor + (size_t)b * T * C::XT;
+            for (int e = li; e < T * C::XT; e += G) gf[e] = tm.Xp[e];
+        }
+        if (li == 0 && a.info && tm.info && a.info[b] == 0) a.info[b] = tm.info;
+    }
+}
+#endif
+
 // ---- backward of the implicit layer -------------------------------------------------
 // DYN: also the gradients w.r.t. the affine dynamics and the initial state (mi_alqp.h, alqp_backward_* with an AlqpBwdDyn). With
 // w = -H^{-1} gbar in ds, s_t = w_{t+1}[x] - F_t w_t in seq (what backward_sweep leaves there as (J d)_eq) and
@@ -563,6 +625,15 @@ int dispatch_step_rows(int nx, int nu, const RowsStepArgs<real> &a, hipStream_t 
         return launch_team_kernel_extra<real, NX, NU>(k_newton_step_rows<real, NX, NU, false>, a.B, a.T, extra, stream, a);
     });
 }
+#elif defined(ALQP_DENSE_STEP_UNIT)
+template <typename real, bool POLY>
+int dispatch_step_dense(int nx, int nu, const DenseStepArgs<real> &a, hipStream_t stream) {
+    const int extra = POLY ? 2 * pad4(a.m) : 0;
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        if (a.xlo) return launch_team_kernel_extra<real, NX, NU>(k_newton_step_dense<real, NX, NU, true, POLY>, a.B, a.T, extra, stream, a);
+        return launch_team_kernel_extra<real, NX, NU>(k_newton_step_dense<real, NX, NU, false, POLY>, a.B, a.T, extra, stream, a);
+    });
+}
 #elif defined(ALQP_SHDYN_UNIT)
 template <typename real>
 int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
@@ -647,13 +718,17 @@ size_t lds_query(int nx, int nu, int T) {
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
 // So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT), the state-bound ones (-DALQP_XBOX_UNIT) and
 // the general-row ones (-DALQP_POLY_UNIT) and the shared-dynamics ones (-DALQP_SHDYN_UNIT), and each combination of flags
-// (-DALQP_GEN_UNIT=<mask>), and the one-step kernels with general rows (-DALQP_ROWS_STEP_UNIT).
+// (-DALQP_GEN_UNIT=<mask>), and the one-step kernels with general rows (-DALQP_ROWS_STEP_UNIT) and with a dense cost
+// (-DALQP_DENSE_STEP_UNIT=<POLY>).
 #if defined(ALQP_GEN_UNIT)
 template int dispatch_solve_gen<float, ALQP_GEN_UNIT>(int, int, const GenSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_gen<double, ALQP_GEN_UNIT>(int, int, const GenSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 #elif defined(ALQP_ROWS_STEP_UNIT)
 template int dispatch_step_rows<float>(int, int, const RowsStepArgs<float> &, hipStream_t);
 template int dispatch_step_rows<double>(int, int, const RowsStepArgs<double> &, hipStream_t);
+#elif defined(ALQP_DENSE_STEP_UNIT)
+template int dispatch_step_dense<float, ALQP_DENSE_STEP_UNIT != 0>(int, int, const DenseStepArgs<float> &, hipStream_t);
+template int dispatch_step_dense<double, ALQP_DENSE_STEP_UNIT != 0>(int, int, const DenseStepArgs<double> &, hipStream_t);
 #elif defined(ALQP_SHDYN_UNIT)
 template int dispatch_solve_shdyn<float>(int, int, const ShdynSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_shdyn<double>(int, int, const ShdynSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);

@@ -172,7 +172,11 @@ class _Launcher:
     # The PyTorch-dynamics route's four launches. With state bounds (xbnd) each goes to its _xbox twin, which takes xbnd
     # behind the control bounds and knows no obstacle rows (the guards of MPC._run keep those apart). With general rows
     # (poly) each goes to its _rows twin, which takes xbnd (None: no state bounds) and poly behind the control bounds.
+    # With a dense cost (Qd is all of C) merit, step and pick go to their _dense twins, which take both (None each); the
+    # dual update reads no cost and keeps its route.
     def merit(self, z, xn, **okw):
+        if self.dense:
+            return self.be.merit_dense(self.dims, 1, z, xn, *self._problem, self.xbnd, self.poly, self.phi, self.rn2, **okw)
         if self.poly is not None:
             return self.be.merit_rows(self.dims, 1, z, xn, *self._problem, self.xbnd, self.poly, self.phi, self.rn2, **okw)
         if self.xbnd is not None:
@@ -180,6 +184,8 @@ class _Launcher:
         self.be.merit(self.dims, 1, z, xn, *self._problem, self.phi, self.rn2, **okw)
 
     def newton_step(self, z, xn, F, **kw):
+        if self.dense:
+            return self.be.newton_step_dense(self.dims, z, xn, F, *self._problem, self.xbnd, self.poly, self.d, **kw)
         if self.poly is not None:
             return self.be.newton_step_rows(self.dims, z, xn, F, *self._problem, self.xbnd, self.poly, self.d, **kw)
         if self.xbnd is not None:
@@ -187,6 +193,9 @@ class _Launcher:
         self.be.newton_step(self.dims, z, xn, F, *self._problem, self.d, **kw)
 
     def merit_pick(self, xn_all, z, **okw):
+        if self.dense:
+            return self.be.merit_pick_dense(self.dims, N_LS, self.d, xn_all, *self._problem, self.xbnd, self.poly, z,
+                                            self.phi, rnorm2=self.rn2, k_out=self.k, accept_out=self.acc, **okw)
         if self.poly is not None:
             return self.be.merit_pick_rows(self.dims, N_LS, self.d, xn_all, *self._problem, self.xbnd, self.poly, z,
                                            self.phi, rnorm2=self.rn2, k_out=self.k, accept_out=self.acc, **okw)
@@ -324,8 +333,12 @@ class MPC(Module):
 
     Differentiable w.r.t. the cost (diag C and c, as the reference). ``diag_cost=False``: C_t is a full matrix (cross
     terms, a Riccati terminal cost, a rotated frame); its symmetric part enters the solve and the gradient reaches all of
-    C. That exists for affine dynamics given as ``LinDx`` only (the fused team kernel), not with a callable ``dx``,
-    ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``. With affine dynamics given as ``LinDx(F, f)`` the solve
+    C. With ``LinDx`` the fused team kernel runs; with a callable ``dx`` / ``dx_jac`` the
+    PyTorch-dynamics route runs with the dense twins of its step, merit and pick kernels (``HipBackend.newton_step_dense``,
+    ``merit_dense``, ``merit_pick_dense``), which take ``x_lower`` / ``x_upper`` and ``ineqG`` / ``ineqh`` too: the direction
+    comes from the team kernel at any batch, a provider with a compiled-in model takes this route, and a backend without
+    ``newton_step_dense`` raises ``NotImplementedError`` for a callable ``dx``. Not with ``linearize_once``,
+    ``state_estimator`` or ``Obstacle_MPC``. With affine dynamics given as ``LinDx(F, f)`` the solve
     is also differentiable w.r.t. ``F``, ``f`` and ``x0`` (see ``_ALSolve``); not on the streaming route
     (``NotImplementedError``). With a callable ``dx`` there are no such gradients: ``x0.grad`` stays ``None``.
 
@@ -346,8 +359,8 @@ class MPC(Module):
     its four kernels (``HipBackend.newton_step_xbox``, ``merit_xbox``, ``merit_pick_xbox``, ``dual_update_xbox``): the
     direction comes from the team kernel at any batch, and a provider with a compiled-in model (``PendulumDynamics``,
     ...) takes this route too. A backend without ``newton_step_xbox`` raises ``NotImplementedError`` for a callable
-    ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``, and on the callable route not with
-    ``diag_cost=False``; with ``ineqG`` see below. The gradients of the route in use stay available (callable ``dx``: ``q`` and
+    ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``; with ``ineqG`` see below, with
+    ``diag_cost=False`` above. The gradients of the route in use stay available (callable ``dx``: ``q`` and
     ``diag(C)``), taken with the active set held fixed.
 
     ``ineqG`` / ``ineqh`` (both or neither): m >= 1 general linear rows G_t tau_t <= h_t per stage, on all
@@ -359,8 +372,7 @@ class MPC(Module):
     of its four kernels (``HipBackend.newton_step_rows``, ``merit_rows``, ``merit_pick_rows``, ``dual_update_rows``),
     which take the state bounds too when both are given: the direction comes from the team kernel at any batch, a
     provider with a compiled-in model takes this route, and a backend without ``newton_step_rows`` raises
-    ``NotImplementedError`` for a callable ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``,
-    and on the callable route not with ``diag_cost=False``. The
+    ``NotImplementedError`` for a callable ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``. The
     gradients above stay available (callable ``dx``: ``q`` and ``diag(C)``), and the solve is also differentiable w.r.t. ``ineqh`` (active set held fixed); an
     ``ineqG`` that requires grad raises ``NotImplementedError``.
 
@@ -393,19 +405,22 @@ class MPC(Module):
             raise ValueError("MPC: x_lower and x_upper go together (pass +-inf for a side without a bound)")
         # combinations of the dense cost, the state bounds and the general rows run on solve_lin_gen; a backend given here
         # is asked now, the default one (resolved lazily) in the guard block of the solve
+        # (with a callable dx the combinations with the dense cost run on the _dense twins of the launch-per-step kernels: a
+        # backend that has them is asked again in the guard block of the solve, where the dynamics are known)
         no_gen = backend is not None and not hasattr(backend, "solve_lin_gen")
+        no_dense_gen = no_gen and not hasattr(backend, "newton_step_dense")
         if x_lower is not None:
             # the state-bound rows live in the fused team kernel of the LinDx routes (alqp_solve_lin_xbox) and in the
             # _xbox twins of the launch-per-step kernels (a callable dx), which have no state-estimator row set
             if state_estimator:
                 raise NotImplementedError("MPC: x_lower / x_upper with state_estimator: the state-bound variants of the "
                                           "nonlinear-caller kernels have no state-estimator row set")
-            if not diag_cost and no_gen:
+            if not diag_cost and no_dense_gen:
                 raise NotImplementedError(_NO_DENSE_XBOX)
         if ineqG is not None or ineqh is not None:
             # the general rows live in the fused team kernel of the LinDx routes (alqp_solve_lin_poly) and in the _rows
             # twins of the launch-per-step kernels (a callable dx), which have no state-estimator row set
-            if not diag_cost and no_gen:   # (before anything is asked of ineqG's shape or of ineqh)
+            if not diag_cost and no_dense_gen:   # (before anything is asked of ineqG's shape or of ineqh)
                 raise NotImplementedError(_NO_DENSE_POLY)
             if ineqG is None or ineqh is None:
                 raise ValueError("MPC: ineqG and ineqh go together")
@@ -854,7 +869,7 @@ class MPC(Module):
         compiled for, and the model's default route unless `prefer_fused`."""
         dx = st.dx
         return (st.lin is None and not st.stream_mode and not self._has_extra_rows() and self.x_lower is None
-                and self.ineqG is None
+                and self.ineqG is None and self.diag_cost   # (nor do they read a dense cost)
                 and getattr(dx, "fused_id", None) is not None
                 and (getattr(dx, "fused_default", True) or self.prefer_fused)
                 and (getattr(dx, "nx", None), getattr(dx, "nu", None)) == (self.n_state, self.n_ctrl))
@@ -889,11 +904,11 @@ class MPC(Module):
         alphas = (2.0 ** -torch.arange(N_LS, device=z.device, dtype=z.dtype)).view(N_LS, 1, 1, 1)
         # from B = QUAD_MIN_BATCH on the direction comes from the quad kernels (obstacle rows / the state-estimator
         # row set included), whose factor stays in the workspace records: the private one when backward follows
-        # With state bounds or general rows the direction comes from the team kernel at any batch (no quad step kernel
-        # knows those rows): no workspace is fetched, and the packed factor is the saved one.
+        # With state bounds, general rows or a dense cost the direction comes from the team kernel at any batch (no quad
+        # step kernel knows those rows or reads a full C): no workspace is fetched, and the packed factor is the saved one.
         qws = L.qws   # (fetched once per solve, on the assumption L.lin_tracked states)
         if (qws is None and L.cached_ws is not None and L.dims[0] >= L.quad_min_batch and L.xbnd is None
-                and L.poly is None):
+                and L.poly is None and not L.dense):
             qws = L.cached_ws(L.dims, z)[0]
         steps = 0
         while steps < MAX_NEWTON:
@@ -1026,26 +1041,30 @@ class MPC(Module):
         if not be.supported(B, T, nx, nu, dt):
             raise RuntimeError(f"mi_alqp: no kernel instance for (nx={nx}, nu={nu}, T={T}, {dt}); "
                                "add it to ALQP_FOR_EACH_DIMS in csrc/alqp_dims.hpp")
+        # a callable dx with a dense cost: the _dense twins of the launch-per-step kernels, which take
+        # the state bounds and the general rows too
+        dense_step = st.lin is None and hasattr(be, "newton_step_dense")
         if not hasattr(be, "solve_lin_gen"):
             # (a backend given to the constructor was refused there; this is the lazily resolved default's turn)
-            if self.x_lower is not None and not self.diag_cost:
+            if self.x_lower is not None and not self.diag_cost and not dense_step:
                 raise NotImplementedError(_NO_DENSE_XBOX)
-            if self.ineqG is not None and not self.diag_cost:
+            if self.ineqG is not None and not self.diag_cost and not dense_step:
                 raise NotImplementedError(_NO_DENSE_POLY)
             # (with a callable dx the two together run on the _rows twins of the launch-per-step kernels alone)
             if self.ineqG is not None and self.x_lower is not None and not (
-                    st.lin is None and hasattr(be, "newton_step_rows")):
+                    st.lin is None and hasattr(be, "newton_step_rows")) and not (not self.diag_cost and dense_step):
                 raise NotImplementedError(_NO_XBOX_POLY)
         if not self.diag_cost:
-            # the dense cost lives in the fused team kernel alone (alqp_solve_lin_dense): everything that reaches the
-            # nonlinear-caller kernels or a compiled-in model reads diag(C)
+            # the dense cost lives in the fused team kernel (alqp_solve_lin_dense) and, for a callable dx, in the _dense
+            # twins of the launch-per-step kernels: the plain nonlinear-caller kernels, the quad step
+            # kernels, the obstacle / state-estimator row sets and the compiled-in models read diag(C)
             if self._has_extra_rows():
                 raise NotImplementedError("MPC: diag_cost=False with obstacle rows / state_estimator: those run on the "
                                           "nonlinear-caller kernels, which read diag(C)")
             if self.linearize_once:
                 raise NotImplementedError("MPC: diag_cost=False with linearize_once: the frozen-linearisation route "
                                           "evaluates merit and dual update with kernels that read diag(C)")
-            if st.lin is None:
+            if st.lin is None and not dense_step:
                 raise NotImplementedError("MPC: diag_cost=False needs affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models read diag(C)")
         if self.x_lower is not None:
@@ -1059,7 +1078,8 @@ class MPC(Module):
                 raise NotImplementedError("MPC: x_lower / x_upper with linearize_once: the frozen-linearisation route "
                                           "is not built with state-bound rows")
             if st.lin is None and not (hasattr(be, "newton_step_xbox")
-                                       or (self.ineqG is not None and hasattr(be, "newton_step_rows"))):
+                                       or (self.ineqG is not None and hasattr(be, "newton_step_rows"))
+                                       or (not self.diag_cost and dense_step)):
                 raise NotImplementedError("MPC: x_lower / x_upper need affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models know no state-bound rows")
             if st.lam.shape[1] != self.neq + self.nineq:
@@ -1075,7 +1095,7 @@ class MPC(Module):
             if self.linearize_once:
                 raise NotImplementedError("MPC: ineqG / ineqh with linearize_once: the frozen-linearisation route "
                                           "evaluates merit and dual update with kernels that know no general rows")
-            if st.lin is None and not hasattr(be, "newton_step_rows"):
+            if st.lin is None and not (hasattr(be, "newton_step_rows") or (not self.diag_cost and dense_step)):
                 raise NotImplementedError("MPC: ineqG / ineqh need affine dynamics given as LinDx(F, f): the "
                                           "nonlinear-caller kernels and the compiled-in models know no general rows")
             if st.lam.shape[1] != self.neq + self.nineq:

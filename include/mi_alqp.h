@@ -485,6 +485,57 @@ int alqp_dual_update_rows_f64(const AlqpDims *dims, const void *z, const void *x
                               void *lam, void *rho, double rho_scale, void *stream);
 
 /*
+ * Newton step, merit and pick with the dense stage cost of alqp_solve_lin_dense_* (1/2 z_t' C_t z_t + q_t' z_t, C [B][T][n][n]
+ * row-major, symmetric, finite), alone or with state box rows and / or general rows: a dense cost with a caller-evaluated
+ * nonlinear model. Each takes its _rows twin's arguments with C where Qd stood. x_lo and x_hi may BOTH be null (no state
+ * bounds); G and h may BOTH be null with m == 0 (no general rows).
+ *   lam [B][T*nx + T*(2nu + XR + m)], XR = 2nx with state bounds and 0 without, m = 0 without general rows.
+ * The dual update reads no cost: alqp_dual_update_*, _xbox_* or _rows_* as the rows demand.
+ * alqp_newton_step_dense_*: the team kernel only - no workspace argument; the packed factor_out is what alqp_backward_*
+ * takes. ALQP_E_UNSUPPORTED for an (nx, nu) that is not compiled and for a horizon (or m) whose LDS image (the team image,
+ * with general rows plus 2 pad4(m) words per team) does not fit; ALQP_E_BADARG for a null C, one of x_lo / x_hi null alone,
+ * G without h or h without G, m outside 1..64 with G, a nonzero m without G, a negative stride, an empty batch, and for
+ * n_ls outside 1..20 in alqp_merit_pick_dense_*.
+ * ADDED under ABI version 17 like the _rows symbols: detect them by symbol lookup.
+ */
+int alqp_newton_step_dense_f32(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
+                               const void *x0, const void *lam, const void *rho, const void *C,
+                               const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                               const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                               const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                               void *d_out, void *g_out, void *factor_out, int *info, void *stream);
+int alqp_newton_step_dense_f64(const AlqpDims *dims, const void *z, const void *xnext, const void *F,
+                               const void *x0, const void *lam, const void *rho, const void *C,
+                               const void *q, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                               const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                               const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                               void *d_out, void *g_out, void *factor_out, int *info, void *stream);
+int alqp_merit_dense_f32(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                         const void *lam, const void *rho, const void *C, const void *q,
+                         const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                         const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                         const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                         void *phi, void *rnorm2, void *stream);
+int alqp_merit_dense_f64(const AlqpDims *dims, int K, const void *zc, const void *xnext, const void *x0,
+                         const void *lam, const void *rho, const void *C, const void *q,
+                         const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                         const void *x_lo, const void *x_hi, long sb_x, long st_x,
+                         const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                         void *phi, void *rnorm2, void *stream);
+int alqp_merit_pick_dense_f32(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                              const void *lam, const void *rho, const void *C, const void *q, const void *u_lo,
+                              const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                              long sb_x, long st_x, const void *G, const void *h, int m, long sb_g, long st_g,
+                              long sb_h, long st_h, void *z, void *phi_prev, void *rnorm2, void *phi_all,
+                              int *k_out, int *accept_out, void *stream);
+int alqp_merit_pick_dense_f64(const AlqpDims *dims, int n_ls, const void *d, const void *xnext_all, const void *x0,
+                              const void *lam, const void *rho, const void *C, const void *q, const void *u_lo,
+                              const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,
+                              long sb_x, long st_x, const void *G, const void *h, int m, long sb_g, long st_g,
+                              long sb_h, long st_h, void *z, void *phi_prev, void *rnorm2, void *phi_all,
+                              int *k_out, int *accept_out, void *stream);
+
+/*
  * Backward of the implicit layer (NewtonAL.backward, al_utils.py:578-615):
  * w = -H^{-1} gbar with the saved factor; q_grad = w, Qd_grad = w * z_final.
  * rho is the penalty the factor was built with. Exactly one of `factor` and `workspace` is non-null:
