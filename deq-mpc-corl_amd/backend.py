@@ -168,9 +168,9 @@ class HipBackend:
         newton_counts (int32 [al_iter], device): with it the reference's batch-global exit test of the Newton loop
         runs INSIDE the launch (ALQP_EXIT_IN_KERNEL, one cooperative launch); returns False - nothing launched - when
         the grid cannot be co-resident (the caller then takes the launch-per-step route), True otherwise."""
-        return self._solve_lin(None, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status,
-                               factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant, workspace, skip,
-                               newton_counts, exit_tol)
+        return self._solve_lin("alqp_solve_lin_", dims, _ptr(Qd, "Qd", z.dtype), q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam,
+                               rho, phi, rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale, trace,
+                               variant, skip, newton_counts, exit_tol, quad=True, workspace=workspace)
 
     def solve_lin_shared(self, dims, Qd, q, F, c, sb_F, st_F, sb_c, st_c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,
                          rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
@@ -184,36 +184,48 @@ class HipBackend:
         for t, name, sb, st, w in ((F, "F", sb_F, st_F, nx * (nx + nu)), (c, "c", sb_c, st_c, nx)):
             if t is not None and min(sb, st) >= 0 and t.numel() < (B - 1) * sb + (T - 2) * st + w:
                 raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
-        return self._solve_lin((sb_F, st_F, sb_c, st_c), dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,
-                               rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant,
-                               workspace, skip, newton_counts, exit_tol)
+        return self._solve_lin("alqp_solve_lin_shared_", dims, _ptr(Qd, "Qd", z.dtype), q, F, c, x0, ulo, uhi, sb_u, st_u, z,
+                               lam, rho, phi, rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale,
+                               trace, variant, skip, newton_counts, exit_tol, quad=True, workspace=workspace,
+                               after_c=(sb_F, st_F, sb_c, st_c))
 
-    def _solve_lin(self, strides, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status,
-                   factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant, workspace, skip, newton_counts,
-                   exit_tol):
-        """solve_lin (strides None: alqp_solve_lin) and solve_lin_shared (strides = (sb_F, st_F, sb_c, st_c):
-        alqp_solve_lin_shared), which differ in the entry point and its four stride arguments alone."""
+    def _solve_lin(self, entry, dims, cost, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status,
+                   factor, al_iter, max_newton, n_ls, flags, rho_scale, trace, variant, skip, newton_counts, exit_tol,
+                   quad=False, workspace=None, after_c=(), after_u=(), after_stream=()):
+        """What the six solve_lin* methods share: the params struct, the exit-in-kernel set-up, the trace struct, the call and
+        the cooperative-launch fallback. entry: the entry point's name without its dtype suffix; cost: its third argument
+        (the pointer to Qd or C, or None); after_c / after_u / after_stream: what it takes behind c, behind st_u and behind
+        the stream. quad: alqp_solve_lin and alqp_solve_lin_shared, the entry points with quad kernels: kernel choice,
+        workspace, debug flags and stagger; the others run the team kernels only."""
         B, T, nx, nu = dims
         dt = z.dtype
-        sfx = _dt(z)
+        name = entry + _dt(z)
         d = _lib.AlqpDims(B, T, nx, nu)
-        if variant is None:
-            variant = self.default_variant
-        vnum = {"auto": 0, "team": 1, "quad": 2}[variant]
-        if vnum == 0:
-            vnum = self._pick_variant(dims, dt, flags)   # 0 (no such instance) goes through: the library refuses it
-        ws, ws_bytes = (None, 0)
-        if vnum == 2:
-            if workspace is not None:
-                ws, ws_bytes = workspace, self.workspace_bytes(*dims, z.dtype)
-                if ws.numel() * ws.element_size() < ws_bytes:
-                    raise ValueError("mi_alqp: workspace too small")
-            else:
-                ws, ws_bytes = self._workspace(dims, z)
-        self.last_variant = "quad" if vnum == 2 else "team"
+        if quad:
+            if variant is None:
+                variant = self.default_variant
+            vnum = {"auto": 0, "team": 1, "quad": 2}[variant]
+            if vnum == 0:
+                vnum = self._pick_variant(dims, dt, flags)   # 0 (no such instance) goes through: the library refuses it
+            ws, ws_bytes = (None, 0)
+            if vnum == 2:
+                if workspace is not None:
+                    ws, ws_bytes = workspace, self.workspace_bytes(*dims, z.dtype)
+                    if ws.numel() * ws.element_size() < ws_bytes:
+                        raise ValueError("mi_alqp: workspace too small")
+                else:
+                    ws, ws_bytes = self._workspace(dims, z)
+            self.last_variant = "quad" if vnum == 2 else "team"
+            flags |= _DEBUG_FLAGS
+            ws_args = (_ptr(ws, "workspace", dt, True), ws_bytes)
+        else:
+            vnum = {"auto": 0, "team": 1, "quad": 2}[variant or "auto"]   # quad goes through: the library refuses it
+            self.last_variant = "team"
+            ws_args = (None, 0) if after_stream else ()   # alqp_solve_lin_gen: alqp_solve_lin's arguments, then its own
         skp = _ptr(skip, "skip", torch.float64, True)
-        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags | _DEBUG_FLAGS, rho_scale, vnum, skp.value if skp is not None else None)
-        p.quad_stagger = {-1: 0, 0: -1}.get(self.quad_stagger, self.quad_stagger)   # ABI: 0 automatic, < 0 off
+        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags, rho_scale, vnum, skp.value if skp is not None else None)
+        if quad:
+            p.quad_stagger = {-1: 0, 0: -1}.get(self.quad_stagger, self.quad_stagger)   # ABI: 0 automatic, < 0 off
         if newton_counts is not None:
             self._exit_in_kernel(p, B, z.device, newton_counts, exit_tol)
         tr = None
@@ -221,19 +233,53 @@ class HipBackend:
             tr = _lib.AlqpTrace(*[
                 (trace[k].data_ptr() if trace.get(k) is not None else None)
                 for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
-        name = ("alqp_solve_lin_" if strides is None else "alqp_solve_lin_shared_") + sfx
         rc = getattr(self.lib, name)(
-            C.byref(d), C.byref(p), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
-            _ptr(c, "c", dt), *(strides or ()), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
-            sb_u, st_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+            C.byref(d), C.byref(p), cost, _ptr(q, "q", dt), _ptr(F, "F", dt),
+            _ptr(c, "c", dt), *after_c, _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
+            sb_u, st_u, *after_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
             _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
             _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
-            _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None,
-            _ptr(ws, "workspace", dt, True), ws_bytes, _stream())
+            _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None, *ws_args, _stream(), *after_stream)
         if rc == _lib.ALQP_E_COOP and newton_counts is not None:
             return False
         _lib.check(rc, name)
         return True
+
+    @staticmethod
+    def _row_checks(dims, lam, dense_C, xbnd, poly, need=None):
+        """The host-side checks of every method that takes a dense cost, state bounds or general rows. dense_C: C or None;
+        xbnd: (xlo, xhi, sb_x, st_x) or None; poly: (G, h, m, sb_g, st_g, sb_h, st_h) or None. C is [B,T,n,n], lam (when
+        given) at least M = T nx + T (2 nu + [2 nx] + [m]) wide, bounds and rows as long as their strides reach. need: how
+        the message names the rows lam is too narrow for, where the method has a wording of its own.
+        -> (xlo, xhi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h), None / 0 for what is absent."""
+        B, T, nx, nu = dims
+        n = nx + nu
+        if dense_C is not None and tuple(dense_C.shape) != (B, T, n, n):
+            raise ValueError(f"mi_alqp: C has shape {tuple(dense_C.shape)}, expected {(B, T, n, n)}")
+        xlo, xhi, sb_x, st_x = xbnd if xbnd is not None else (None, None, 0, 0)
+        G, h, m, sb_g, st_g, sb_h, st_h = poly if poly is not None else (None, None, 0, 0, 0, 0, 0)
+        M = T * nx + T * (2 * nu + (2 * nx if xbnd is not None else 0) + (max(int(m), 0) if poly is not None else 0))
+        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
+            if need is None:
+                need = "these rows need" if poly is not None else "the state-bound rows need" if xbnd is not None else "expected"
+            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, {need} [B, {M}]")
+        if xbnd is not None:
+            for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
+                if t is None:
+                    raise ValueError(f"mi_alqp: {name} is required")
+                if min(sb_x, st_x) >= 0 and t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
+                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
+        for t, name, sb, st, w in ((G, "ineqG", sb_g, st_g, m * n), (h, "ineqh", sb_h, st_h, m)):
+            if t is not None and m >= 1 and min(sb, st) >= 0 and t.numel() < (B - 1) * sb + (T - 1) * st + w:
+                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
+        return xlo, xhi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h
+
+    @staticmethod
+    def _rows_cargs(rows, dt):
+        """_row_checks' tuple as the C arguments from x_lo to st_h."""
+        xlo, xhi, sb_x, st_x, G, h, *rest = rows
+        return (_ptr(xlo, "x_lower", dt, True), _ptr(xhi, "x_upper", dt, True), sb_x, st_x,
+                _ptr(G, "ineqG", dt, True), _ptr(h, "ineqh", dt, True), *rest)
 
     def solve_lin_dense(self, dims, Cs, q, F, c, x0, ulo, uhi, sb_u, st_u, z, lam, rho, phi,
                         rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
@@ -241,35 +287,10 @@ class HipBackend:
                         trace=None, variant=None, skip=None, newton_counts=None, exit_tol=1e-3):
         """solve_lin with a dense stage cost (alqp_solve_lin_dense): Cs [B,T,n,n], symmetric, in place of Qd. Team
         kernel only (variant None / "auto" / "team"), no workspace; everything else as solve_lin."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        n = nx + nu
-        if tuple(Cs.shape) != (B, T, n, n):
-            raise ValueError(f"mi_alqp: C has shape {tuple(Cs.shape)}, expected {(B, T, n, n)}")
-        d = _lib.AlqpDims(B, T, nx, nu)
-        vnum = {"auto": 0, "team": 1, "quad": 2}[variant or "auto"]   # quad goes through: the library refuses it
-        self.last_variant = "team"
-        skp = _ptr(skip, "skip", torch.float64, True)
-        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags, rho_scale, vnum, skp.value if skp is not None else None)
-        if newton_counts is not None:
-            self._exit_in_kernel(p, B, z.device, newton_counts, exit_tol)
-        tr = None
-        if trace is not None:
-            tr = _lib.AlqpTrace(*[
-                (trace[k].data_ptr() if trace.get(k) is not None else None)
-                for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
-        fn = getattr(self.lib, "alqp_solve_lin_dense_" + sfx)
-        rc = fn(C.byref(d), C.byref(p), _ptr(Cs, "C", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
-                _ptr(c, "c", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
-                sb_u, st_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
-                _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
-                _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
-                _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None, _stream())
-        if rc == _lib.ALQP_E_COOP and newton_counts is not None:
-            return False
-        _lib.check(rc, "alqp_solve_lin_dense_" + sfx)
-        return True
+        self._row_checks(dims, None, Cs, None, None)
+        return self._solve_lin("alqp_solve_lin_dense_", dims, _ptr(Cs, "C", z.dtype), q, F, c, x0, ulo, uhi, sb_u, st_u, z,
+                               lam, rho, phi, rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale,
+                               trace, variant, skip, newton_counts, exit_tol)
 
     def solve_lin_xbox(self, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, xlo, xhi, sb_x, st_x, z, lam, rho, phi,
                        rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
@@ -279,41 +300,10 @@ class HipBackend:
         or [B,T,nx] (sb_x = T nx, st_x = nx), finite. lam is [B, T nx + T (2 nu + 2 nx)]: per stage
         [u - uhi | -u + ulo | x - xhi | -x + xlo] behind the equality rows. Team kernel only (variant None / "auto" /
         "team"), no workspace; everything else as solve_lin."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        M = T * nx + T * (2 * nu + 2 * nx)
-        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
-            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, the state-bound rows need [B, {M}]")
-        for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
-            if t is None:
-                raise ValueError(f"mi_alqp: {name} is required")
-            if t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
-                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
-        d = _lib.AlqpDims(B, T, nx, nu)
-        vnum = {"auto": 0, "team": 1, "quad": 2}[variant or "auto"]   # quad goes through: the library refuses it
-        self.last_variant = "team"
-        skp = _ptr(skip, "skip", torch.float64, True)
-        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags, rho_scale, vnum, skp.value if skp is not None else None)
-        if newton_counts is not None:
-            self._exit_in_kernel(p, B, z.device, newton_counts, exit_tol)
-        tr = None
-        if trace is not None:
-            tr = _lib.AlqpTrace(*[
-                (trace[k].data_ptr() if trace.get(k) is not None else None)
-                for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
-        fn = getattr(self.lib, "alqp_solve_lin_xbox_" + sfx)
-        rc = fn(C.byref(d), C.byref(p), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
-                _ptr(c, "c", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
-                sb_u, st_u, _ptr(xlo, "x_lower", dt), _ptr(xhi, "x_upper", dt), sb_x, st_x,
-                _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
-                _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
-                _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
-                _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None, _stream())
-        if rc == _lib.ALQP_E_COOP and newton_counts is not None:
-            return False
-        _lib.check(rc, "alqp_solve_lin_xbox_" + sfx)
-        return True
+        rows = self._row_checks(dims, lam, None, (xlo, xhi, sb_x, st_x), None)
+        return self._solve_lin("alqp_solve_lin_xbox_", dims, _ptr(Qd, "Qd", z.dtype), q, F, c, x0, ulo, uhi, sb_u, st_u, z,
+                               lam, rho, phi, rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale,
+                               trace, variant, skip, newton_counts, exit_tol, after_u=self._rows_cargs(rows, z.dtype)[:4])
 
     def solve_lin_poly(self, dims, Qd, q, F, c, x0, ulo, uhi, sb_u, st_u, G, h, m, sb_g, st_g, sb_h, st_h, z, lam, rho, phi,
                        rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
@@ -323,40 +313,10 @@ class HipBackend:
         st_g = 0), [T,m,n] (0, m n) or [B,T,m,n] (T m n, m n), h likewise without the last axis, finite. lam is
         [B, T nx + T (2 nu + m)]: per stage [u - uhi | -u + ulo | G_t z_t - h_t] behind the equality rows. Team kernel
         only (variant None / "auto" / "team"), no workspace; everything else as solve_lin."""
-        B, T, nx, nu = dims
-        n = nx + nu
-        dt = z.dtype
-        sfx = _dt(z)
-        M = T * nx + T * (2 * nu + max(int(m), 0))
-        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
-            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, the general rows need [B, {M}]")
-        for t, name, sb, st, w in ((G, "ineqG", sb_g, st_g, m * n), (h, "ineqh", sb_h, st_h, m)):
-            if t is not None and m >= 1 and t.numel() < (B - 1) * sb + (T - 1) * st + w:
-                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
-        d = _lib.AlqpDims(B, T, nx, nu)
-        vnum = {"auto": 0, "team": 1, "quad": 2}[variant or "auto"]   # quad goes through: the library refuses it
-        self.last_variant = "team"
-        skp = _ptr(skip, "skip", torch.float64, True)
-        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags, rho_scale, vnum, skp.value if skp is not None else None)
-        if newton_counts is not None:
-            self._exit_in_kernel(p, B, z.device, newton_counts, exit_tol)
-        tr = None
-        if trace is not None:
-            tr = _lib.AlqpTrace(*[
-                (trace[k].data_ptr() if trace.get(k) is not None else None)
-                for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
-        fn = getattr(self.lib, "alqp_solve_lin_poly_" + sfx)
-        rc = fn(C.byref(d), C.byref(p), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
-                _ptr(c, "c", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
-                sb_u, st_u, _ptr(G, "ineqG", dt, True), _ptr(h, "ineqh", dt, True), m, sb_g, st_g, sb_h, st_h,
-                _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
-                _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
-                _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
-                _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None, _stream())
-        if rc == _lib.ALQP_E_COOP and newton_counts is not None:
-            return False
-        _lib.check(rc, "alqp_solve_lin_poly_" + sfx)
-        return True
+        rows = self._row_checks(dims, lam, None, None, (G, h, m, sb_g, st_g, sb_h, st_h), "the general rows need")
+        return self._solve_lin("alqp_solve_lin_poly_", dims, _ptr(Qd, "Qd", z.dtype), q, F, c, x0, ulo, uhi, sb_u, st_u, z,
+                               lam, rho, phi, rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags, rho_scale,
+                               trace, variant, skip, newton_counts, exit_tol, after_u=self._rows_cargs(rows, z.dtype)[4:])
 
     def solve_lin_gen(self, dims, Qd_or_C, q, F, c, x0, ulo, uhi, sb_u, st_u, xbnd, poly, z, lam, rho, phi,
                       rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
@@ -367,53 +327,13 @@ class HipBackend:
         or None; poly: (G, h, m, sb_g, st_g, sb_h, st_h) as solve_lin_poly takes them, or None. lam is
         [B, T nx + T (2 nu + [2 nx] + [m])]: per stage [u - uhi | -u + ulo | x - xhi | -x + xlo | G_t z_t - h_t] behind the
         equality rows. Team kernel only (variant None / "auto" / "team"), no workspace; everything else as solve_lin."""
-        B, T, nx, nu = dims
-        n = nx + nu
         dt = z.dtype
-        sfx = _dt(z)
         dense = Qd_or_C is not None and Qd_or_C.dim() == 4
-        if dense and tuple(Qd_or_C.shape) != (B, T, n, n):
-            raise ValueError(f"mi_alqp: C has shape {tuple(Qd_or_C.shape)}, expected {(B, T, n, n)}")
-        xlo, xhi, sb_x, st_x = xbnd if xbnd is not None else (None, None, 0, 0)
-        G, h, m, sb_g, st_g, sb_h, st_h = poly if poly is not None else (None, None, 0, 0, 0, 0, 0)
-        M = T * nx + T * (2 * nu + (2 * nx if xbnd is not None else 0) + (max(int(m), 0) if poly is not None else 0))
-        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
-            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, these rows need [B, {M}]")
-        if xbnd is not None:
-            for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
-                if t is None:
-                    raise ValueError(f"mi_alqp: {name} is required")
-                if t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
-                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
-        if poly is not None:
-            for t, name, sb, st, w in ((G, "ineqG", sb_g, st_g, m * n), (h, "ineqh", sb_h, st_h, m)):
-                if t is not None and m >= 1 and t.numel() < (B - 1) * sb + (T - 1) * st + w:
-                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
-        d = _lib.AlqpDims(B, T, nx, nu)
-        vnum = {"auto": 0, "team": 1, "quad": 2}[variant or "auto"]   # quad goes through: the library refuses it
-        self.last_variant = "team"
-        skp = _ptr(skip, "skip", torch.float64, True)
-        p = _lib.AlqpParams(al_iter, max_newton, n_ls, flags, rho_scale, vnum, skp.value if skp is not None else None)
-        if newton_counts is not None:
-            self._exit_in_kernel(p, B, z.device, newton_counts, exit_tol)
-        tr = None
-        if trace is not None:
-            tr = _lib.AlqpTrace(*[
-                (trace[k].data_ptr() if trace.get(k) is not None else None)
-                for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
-        fn = getattr(self.lib, "alqp_solve_lin_gen_" + sfx)
-        rc = fn(C.byref(d), C.byref(p), None if dense else _ptr(Qd_or_C, "Qd", dt), _ptr(q, "q", dt), _ptr(F, "F", dt),
-                _ptr(c, "c", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt),
-                sb_u, st_u, _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
-                _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True),
-                _ptr(info, "info", torch.int32, True), _ptr(status, "status", torch.uint8, True),
-                _ptr(factor, "factor", dt, True), C.byref(tr) if tr is not None else None, None, 0, _stream(),
-                _ptr(Qd_or_C, "C", dt) if dense else None, _ptr(xlo, "x_lower", dt, True), _ptr(xhi, "x_upper", dt, True),
-                sb_x, st_x, _ptr(G, "ineqG", dt, True), _ptr(h, "ineqh", dt, True), m, sb_g, st_g, sb_h, st_h)
-        if rc == _lib.ALQP_E_COOP and newton_counts is not None:
-            return False
-        _lib.check(rc, "alqp_solve_lin_gen_" + sfx)
-        return True
+        rows = self._row_checks(dims, lam, Qd_or_C if dense else None, xbnd, poly, "these rows need")
+        return self._solve_lin("alqp_solve_lin_gen_", dims, None if dense else _ptr(Qd_or_C, "Qd", dt), q, F, c, x0, ulo, uhi,
+                               sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, factor, al_iter, max_newton, n_ls, flags,
+                               rho_scale, trace, variant, skip, newton_counts, exit_tol,
+                               after_stream=(_ptr(Qd_or_C, "C", dt) if dense else None, *self._rows_cargs(rows, dt)))
 
     def _exit_in_kernel(self, p, B, device, newton_counts, exit_tol):
         """AlqpParams fields of ALQP_EXIT_IN_KERNEL: the cached scratch (arrival counter + 2 x B partial sums)."""
@@ -615,243 +535,132 @@ class HipBackend:
             _ptr(rho, "rho", dt), rho_scale, _stream())
         _lib.check(rc, "alqp_dual_update_" + sfx)
 
-    # -- the same four with state box rows (alqp_*_xbox): MPC(x_lower=, x_upper=) with a callable dx -----------------
-    @staticmethod
-    def _xbox_checks(dims, lam, xbnd):
-        """The host-side checks solve_lin_xbox makes: lam at least M = T nx + T (2 nu + 2 nx) wide, the bounds as long as
-        their strides reach. -> (xlo, xhi, sb_x, st_x)."""
-        B, T, nx, nu = dims
-        xlo, xhi, sb_x, st_x = xbnd
-        M = T * nx + T * (2 * nu + 2 * nx)
-        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
-            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, the state-bound rows need [B, {M}]")
-        for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
-            if t is None:
-                raise ValueError(f"mi_alqp: {name} is required")
-            if min(sb_x, st_x) >= 0 and t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
-                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
-        return xlo, xhi, sb_x, st_x
+    # -- the same four with more rows per stage and / or a dense stage cost, for MPC with a callable dx. Three families of
+    # entry points: alqp_*_xbox (state box rows; x_lower=, x_upper=), alqp_*_rows (general rows, with or without state box
+    # rows; ineqG=, ineqh=) and alqp_*_dense (a dense stage cost, with or without either; diag_cost=False). One private method
+    # per call shape, the named methods below are its callers. fam: "xbox", "rows" or "dense"; cost: Qd, or C for "dense";
+    # xbnd = (xlo, xhi, sb_x, st_x) or None; poly = (G, h, m, sb_g, st_g, sb_h, st_h) or None. The dual update reads no
+    # cost: dual_update, _xbox or _rows ------------------------------------------------------------------------------------
+    def _fam_cargs(self, fam, dims, lam, cost, xbnd, poly, dt):
+        """_row_checks, then the family's C arguments behind st_u: from x_lo to st_x (xbox) or to st_h."""
+        rows = self._rows_cargs(self._row_checks(dims, lam, cost if fam == "dense" else None, xbnd, poly), dt)
+        return rows[:4] if fam == "xbox" else rows
+
+    def _step_fam(self, fam, dims, z, xnext, F, x0, lam, rho, cost, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out, g_out, factor,
+                  info):
+        dt = z.dtype
+        name = f"alqp_newton_step_{fam}_" + _dt(z)
+        rows = self._fam_cargs(fam, dims, lam, cost, xbnd, poly, dt)
+        d = _lib.AlqpDims(*dims)
+        rc = getattr(self.lib, name)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+            _ptr(cost, "C" if fam == "dense" else "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(d_out, "d_out", dt),
+            _ptr(g_out, "g_out", dt, True), _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True),
+            _stream())
+        _lib.check(rc, name)
+        self.last_step_kernel = "k_newton_step_" + fam
+
+    def _merit_fam(self, fam, dims, K, zc, xnext, x0, lam, rho, cost, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2):
+        dt = zc.dtype
+        name = f"alqp_merit_{fam}_" + _dt(zc)
+        rows = self._fam_cargs(fam, dims, lam, cost, xbnd, poly, dt)
+        d = _lib.AlqpDims(*dims)
+        rc = getattr(self.lib, name)(
+            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+            _ptr(cost, "C" if fam == "dense" else "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(phi, "phi", dt),
+            _ptr(rnorm2, "rnorm2", dt, True), _stream())
+        _lib.check(rc, name)
+
+    def _merit_pick_fam(self, fam, dims, n_ls, d, xnext_all, x0, lam, rho, cost, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
+                        phi_prev, rnorm2, phi_all, k_out, accept_out):
+        dt = z.dtype
+        name = f"alqp_merit_pick_{fam}_" + _dt(z)
+        rows = self._fam_cargs(fam, dims, lam, cost, xbnd, poly, dt)
+        dd = _lib.AlqpDims(*dims)
+        rc = getattr(self.lib, name)(
+            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
+            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+            _ptr(cost, "C" if fam == "dense" else "Qd", dt), _ptr(q, "q", dt),
+            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(z, "z", dt),
+            _ptr(phi_prev, "phi_prev", dt), _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
+            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
+        _lib.check(rc, name)
+
+    def _dual_fam(self, fam, dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, poly, lam, rho, rho_scale):
+        dt = z.dtype
+        name = f"alqp_dual_update_{fam}_" + _dt(z)
+        rows = self._fam_cargs(fam, dims, lam, None, xbnd, poly, dt)
+        d = _lib.AlqpDims(*dims)
+        rc = getattr(self.lib, name)(
+            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt),
+            _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale,
+            _stream())
+        _lib.check(rc, name)
 
     def newton_step_xbox(self, dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, d_out,
                          g_out=None, factor=None, info=None):
         """newton_step with state box rows (alqp_newton_step_xbox): xbnd = (xlo, xhi, sb_x, st_x) as solve_lin_xbox takes
         them, lam [B, T nx + T (2 nu + 2 nx)]. The team kernel at any batch (no workspace), optional packed `factor`."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_newton_step_xbox_" + sfx)(
-            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt),
-            _ptr(xhi, "x_upper", dt), sb_x, st_x, _ptr(d_out, "d_out", dt), _ptr(g_out, "g_out", dt, True),
-            _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True), _stream())
-        _lib.check(rc, "alqp_newton_step_xbox_" + sfx)
-        self.last_step_kernel = "k_newton_step_xbox"
+        self._step_fam("xbox", dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, None, d_out, g_out,
+                       factor, info)
 
     def merit_xbox(self, dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, phi, rnorm2=None):
         """merit with state box rows (alqp_merit_xbox); xbnd and lam as newton_step_xbox."""
-        B, T, nx, nu = dims
-        dt = zc.dtype
-        sfx = _dt(zc)
-        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_merit_xbox_" + sfx)(
-            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt),
-            _ptr(xhi, "x_upper", dt), sb_x, st_x, _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True), _stream())
-        _lib.check(rc, "alqp_merit_xbox_" + sfx)
+        self._merit_fam("xbox", dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, None, phi, rnorm2)
 
     def merit_pick_xbox(self, dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, z, phi_prev,
                         rnorm2=None, phi_all=None, k_out=None, accept_out=None):
         """merit_pick with state box rows (alqp_merit_pick_xbox); xbnd and lam as newton_step_xbox."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
-        dd = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_merit_pick_xbox_" + sfx)(
-            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt),
-            _ptr(xhi, "x_upper", dt), sb_x, st_x, _ptr(z, "z", dt), _ptr(phi_prev, "phi_prev", dt),
-            _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
-            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
-        _lib.check(rc, "alqp_merit_pick_xbox_" + sfx)
+        self._merit_pick_fam("xbox", dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, None, z,
+                             phi_prev, rnorm2, phi_all, k_out, accept_out)
 
     def dual_update_xbox(self, dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, lam, rho, rho_scale=10.0):
         """dual_update with state box rows (alqp_dual_update_xbox); xbnd and lam as newton_step_xbox."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        xlo, xhi, sb_x, st_x = self._xbox_checks(dims, lam, xbnd)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_dual_update_xbox_" + sfx)(
-            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt),
-            _ptr(uhi, "u_upper", dt), sb_u, st_u, _ptr(xlo, "x_lower", dt), _ptr(xhi, "x_upper", dt), sb_x, st_x,
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale, _stream())
-        _lib.check(rc, "alqp_dual_update_xbox_" + sfx)
-
-    # -- the same four with general rows, with or without state box rows (alqp_*_rows): MPC(ineqG=, ineqh=) with a
-    # callable dx ------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _rows_checks(dims, lam, xbnd, poly):
-        """The host-side checks solve_lin_poly / solve_lin_gen make: lam at least M = T nx + T (2 nu + [2 nx] + m) wide,
-        bounds and rows as long as their strides reach. -> (xlo, xhi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h)."""
-        B, T, nx, nu = dims
-        n = nx + nu
-        xlo, xhi, sb_x, st_x = xbnd if xbnd is not None else (None, None, 0, 0)
-        G, h, m, sb_g, st_g, sb_h, st_h = poly
-        M = T * nx + T * (2 * nu + (2 * nx if xbnd is not None else 0) + max(int(m), 0))
-        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
-            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, these rows need [B, {M}]")
-        if xbnd is not None:
-            for t, name in ((xlo, "x_lower"), (xhi, "x_upper")):
-                if t is None:
-                    raise ValueError(f"mi_alqp: {name} is required")
-                if min(sb_x, st_x) >= 0 and t.numel() < (B - 1) * sb_x + (T - 1) * st_x + nx:
-                    raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb_x}, {st_x})")
-        for t, name, sb, st, w in ((G, "ineqG", sb_g, st_g, m * n), (h, "ineqh", sb_h, st_h, m)):
-            if t is not None and m >= 1 and min(sb, st) >= 0 and t.numel() < (B - 1) * sb + (T - 1) * st + w:
-                raise ValueError(f"mi_alqp: {name} has {t.numel()} elements, too few for strides ({sb}, {st})")
-        return xlo, xhi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h
-
-    @staticmethod
-    def _rows_cargs(rows, dt):
-        """_rows_checks' tuple as the C arguments from x_lo to st_h."""
-        xlo, xhi, sb_x, st_x, G, h, *rest = rows
-        return (_ptr(xlo, "x_lower", dt, True), _ptr(xhi, "x_upper", dt, True), sb_x, st_x,
-                _ptr(G, "ineqG", dt, True), _ptr(h, "ineqh", dt, True), *rest)
+        self._dual_fam("xbox", dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, None, lam, rho, rho_scale)
 
     def newton_step_rows(self, dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out,
                          g_out=None, factor=None, info=None):
         """newton_step with general rows (alqp_newton_step_rows): poly = (G, h, m, sb_g, st_g, sb_h, st_h) as
         solve_lin_poly takes them, xbnd = (xlo, xhi, sb_x, st_x) or None (no state bounds),
         lam [B, T nx + T (2 nu + [2 nx] + m)]. The team kernel at any batch (no workspace), optional packed `factor`."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_newton_step_rows_" + sfx)(
-            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(d_out, "d_out", dt),
-            _ptr(g_out, "g_out", dt, True), _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True),
-            _stream())
-        _lib.check(rc, "alqp_newton_step_rows_" + sfx)
-        self.last_step_kernel = "k_newton_step_rows"
+        self._step_fam("rows", dims, z, xnext, F, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out, g_out,
+                       factor, info)
 
     def merit_rows(self, dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2=None):
         """merit with general rows (alqp_merit_rows); xbnd, poly and lam as newton_step_rows."""
-        B, T, nx, nu = dims
-        dt = zc.dtype
-        sfx = _dt(zc)
-        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_merit_rows_" + sfx)(
-            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(phi, "phi", dt),
-            _ptr(rnorm2, "rnorm2", dt, True), _stream())
-        _lib.check(rc, "alqp_merit_rows_" + sfx)
+        self._merit_fam("rows", dims, K, zc, xnext, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2)
 
     def merit_pick_rows(self, dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
                         phi_prev, rnorm2=None, phi_all=None, k_out=None, accept_out=None):
         """merit_pick with general rows (alqp_merit_pick_rows); xbnd, poly and lam as newton_step_rows."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
-        dd = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_merit_pick_rows_" + sfx)(
-            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Qd, "Qd", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(z, "z", dt),
-            _ptr(phi_prev, "phi_prev", dt), _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
-            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
-        _lib.check(rc, "alqp_merit_pick_rows_" + sfx)
+        self._merit_pick_fam("rows", dims, n_ls, d, xnext_all, x0, lam, rho, Qd, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
+                             phi_prev, rnorm2, phi_all, k_out, accept_out)
 
     def dual_update_rows(self, dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, poly, lam, rho, rho_scale=10.0):
         """dual_update with general rows (alqp_dual_update_rows); xbnd, poly and lam as newton_step_rows."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        rows = self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_dual_update_rows_" + sfx)(
-            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt),
-            _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), rho_scale,
-            _stream())
-        _lib.check(rc, "alqp_dual_update_rows_" + sfx)
-
-    # -- step, merit and pick with a dense stage cost, with or without state box rows and general rows (alqp_*_dense):
-    # MPC(diag_cost=False) with a callable dx. The dual update reads no cost: dual_update, _xbox or _rows ---------------
-    def _dense_cargs(self, dims, lam, Cs, xbnd, poly, dt):
-        """solve_lin_dense's check on Cs with _xbox_checks / _rows_checks on the rows -> the C arguments from x_lo to st_h."""
-        B, T, nx, nu = dims
-        n = nx + nu
-        if tuple(Cs.shape) != (B, T, n, n):
-            raise ValueError(f"mi_alqp: C has shape {tuple(Cs.shape)}, expected {(B, T, n, n)}")
-        if poly is not None:
-            return self._rows_cargs(self._rows_checks(dims, lam, xbnd, poly), dt)
-        if xbnd is not None:
-            return self._rows_cargs((*self._xbox_checks(dims, lam, xbnd), None, None, 0, 0, 0, 0, 0), dt)
-        M = T * nx + 2 * T * nu
-        if lam is not None and (lam.dim() != 2 or lam.shape[0] != B or lam.shape[1] < M):
-            raise ValueError(f"mi_alqp: lam has shape {tuple(lam.shape)}, expected [B, {M}]")
-        return (None, None, 0, 0, None, None, 0, 0, 0, 0, 0)
+        self._dual_fam("rows", dims, z, xnext, x0, ulo, uhi, sb_u, st_u, xbnd, poly, lam, rho, rho_scale)
 
     def newton_step_dense(self, dims, z, xnext, F, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out,
                           g_out=None, factor=None, info=None):
         """newton_step with a dense stage cost (alqp_newton_step_dense): Cs [B,T,n,n], symmetric, in place of Qd;
         xbnd = (xlo, xhi, sb_x, st_x) or None, poly = (G, h, m, sb_g, st_g, sb_h, st_h) or None,
         lam [B, T nx + T (2 nu + [2 nx] + [m])]. The team kernel at any batch (no workspace), optional packed `factor`."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        rows = self._dense_cargs(dims, lam, Cs, xbnd, poly, dt)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_newton_step_dense_" + sfx)(
-            C.byref(d), _ptr(z, "z", dt), _ptr(xnext, "xnext", dt), _ptr(F, "F", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Cs, "C", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(d_out, "d_out", dt),
-            _ptr(g_out, "g_out", dt, True), _ptr(factor, "factor", dt, True), _ptr(info, "info", torch.int32, True),
-            _stream())
-        _lib.check(rc, "alqp_newton_step_dense_" + sfx)
-        self.last_step_kernel = "k_newton_step_dense"
+        self._step_fam("dense", dims, z, xnext, F, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, d_out, g_out,
+                       factor, info)
 
     def merit_dense(self, dims, K, zc, xnext, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2=None):
         """merit with a dense stage cost (alqp_merit_dense); Cs, xbnd, poly and lam as newton_step_dense."""
-        B, T, nx, nu = dims
-        dt = zc.dtype
-        sfx = _dt(zc)
-        rows = self._dense_cargs(dims, lam, Cs, xbnd, poly, dt)
-        d = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_merit_dense_" + sfx)(
-            C.byref(d), K, _ptr(zc, "zc", dt), _ptr(xnext, "xnext", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Cs, "C", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(phi, "phi", dt),
-            _ptr(rnorm2, "rnorm2", dt, True), _stream())
-        _lib.check(rc, "alqp_merit_dense_" + sfx)
+        self._merit_fam("dense", dims, K, zc, xnext, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, phi, rnorm2)
 
     def merit_pick_dense(self, dims, n_ls, d, xnext_all, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
                          phi_prev, rnorm2=None, phi_all=None, k_out=None, accept_out=None):
         """merit_pick with a dense stage cost (alqp_merit_pick_dense); Cs, xbnd, poly and lam as newton_step_dense."""
-        B, T, nx, nu = dims
-        dt = z.dtype
-        sfx = _dt(z)
-        rows = self._dense_cargs(dims, lam, Cs, xbnd, poly, dt)
-        dd = _lib.AlqpDims(B, T, nx, nu)
-        rc = getattr(self.lib, "alqp_merit_pick_dense_" + sfx)(
-            C.byref(dd), n_ls, _ptr(d, "d", dt), _ptr(xnext_all, "xnext_all", dt), _ptr(x0, "x0", dt),
-            _ptr(lam, "lam", dt), _ptr(rho, "rho", dt), _ptr(Cs, "C", dt), _ptr(q, "q", dt),
-            _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u, *rows, _ptr(z, "z", dt),
-            _ptr(phi_prev, "phi_prev", dt), _ptr(rnorm2, "rnorm2", dt, True), _ptr(phi_all, "phi_all", dt, True),
-            _ptr(k_out, "k_out", torch.int32, True), _ptr(accept_out, "accept_out", torch.int32, True), _stream())
-        _lib.check(rc, "alqp_merit_pick_dense_" + sfx)
+        self._merit_pick_fam("dense", dims, n_ls, d, xnext_all, x0, lam, rho, Cs, q, ulo, uhi, sb_u, st_u, xbnd, poly, z,
+                             phi_prev, rnorm2, phi_all, k_out, accept_out)
 
     def _backward(self, dims, factor, workspace, ws_bytes, F, rho, z_final, gbar, q_grad, Qd_grad, dyn):
         """alqp_backward_*: `factor` or `workspace` is a device pointer, the other None."""

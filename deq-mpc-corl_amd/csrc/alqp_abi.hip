@@ -3,6 +3,8 @@
 // No torch types anywhere: plain device pointers in, kernel launches on the caller's stream.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "alqp_team.hpp"   // Cfg
 #include "alqp_quad.hpp"   // QCfg
 #include "alqp_dims.hpp"
@@ -368,87 +370,50 @@ int newton_step_impl(const AlqpDims *dims, const void *z, const void *xnext, con
     return dispatch_step<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
 }
 
-// One Newton direction with state box rows: the team kernel only (no quad step kernel knows such rows), so no workspace,
-// and the horizon must fit the team's LDS image like alqp_solve_lin_xbox's.
-template <typename real>
-int newton_step_xbox_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *F, const void *x0,
-                          const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
-                          const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
-                          long st_x, void *d_out, void *g_out, void *factor_out, int *info, void *stream) {
-    if (!dims_ok(dims) || !z || !xnext || !F || !x0 || !lam || !rho || !Qd || !q || !u_lo || !u_hi || !x_lo || !x_hi ||
-        !d_out)
+// One Newton direction with more rows per stage and / or a dense stage cost: alqp_newton_step_xbox (Args = XboxStepArgs),
+// _rows (RowsStepArgs) and _dense (DenseStepArgs, `cost` is C). The team kernel only (no quad step kernel knows such rows), so
+// no workspace, and the horizon must fit the team's LDS image like alqp_solve_lin_xbox's; with general rows the image grows by
+// the hand-over region of 2 pad4(m) words per team, like alqp_solve_lin_poly's. _xbox: both state bounds and no rows. _rows:
+// x_lo and x_hi both null (no state box rows) or neither; G, h and m in 1..64. _dense: the same state bounds; G and h both
+// null with m == 0 (no general rows) or neither.
+template <typename real, typename Args>
+int newton_step_ext_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *F, const void *x0,
+                         const void *lam, const void *rho, const void *cost, const void *q, const void *u_lo,
+                         const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
+                         long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
+                         void *d_out, void *g_out, void *factor_out, int *info, void *stream) {
+    constexpr bool kXbox = std::is_same_v<Args, XboxStepArgs<real>>, kDense = std::is_same_v<Args, DenseStepArgs<real>>;
+    if (!dims_ok(dims) || !z || !xnext || !F || !x0 || !lam || !rho || !cost || !q || !u_lo || !u_hi || !d_out)
         return ALQP_E_BADARG;
-    if (sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
-    const size_t lds = lds_query<real>(dims->nx, dims->nu, dims->T);
-    if (lds == 0 || lds > kMaxLds) return ALQP_E_UNSUPPORTED;
-    XboxStepArgs<real> a = {};
-    a.B = dims->B; a.T = dims->T;
-    a.z = (const real *)z; a.xnext = (const real *)xnext; a.F = (const real *)F; a.x0 = (const real *)x0;
-    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
-    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
-    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
-    a.d_out = (real *)d_out; a.g_out = (real *)g_out; a.factor = (real *)factor_out; a.info = info;
-    return dispatch_step_xbox<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
-}
-
-// One Newton direction with general rows, with (x_lo, x_hi) or without (both null) state box rows: the team kernel only, no
-// workspace; the LDS image is the team image plus the hand-over region of 2 pad4(m) words per team, like alqp_solve_lin_poly's.
-template <typename real>
-int newton_step_rows_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *F, const void *x0,
-                          const void *lam, const void *rho, const void *Qd, const void *q, const void *u_lo,
-                          const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
-                          long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
-                          void *d_out, void *g_out, void *factor_out, int *info, void *stream) {
-    if (!dims_ok(dims) || !z || !xnext || !F || !x0 || !lam || !rho || !Qd || !q || !u_lo || !u_hi || !G || !h || !d_out)
-        return ALQP_E_BADARG;
-    if (!x_lo != !x_hi || sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
-    if (m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) return ALQP_E_BADARG;
-    const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
-    if (img == 0) return ALQP_E_UNSUPPORTED;
-    const size_t lds = img + (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real);
-    if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
-    RowsStepArgs<real> a = {};
-    a.B = dims->B; a.T = dims->T;
-    a.z = (const real *)z; a.xnext = (const real *)xnext; a.F = (const real *)F; a.x0 = (const real *)x0;
-    a.lam = (const real *)lam; a.rho = (const real *)rho; a.Qd = (const real *)Qd; a.q = (const real *)q;
-    a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
-    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
-    a.G = (const real *)G; a.h = (const real *)h; a.m = m;
-    a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
-    a.d_out = (real *)d_out; a.g_out = (real *)g_out; a.factor = (real *)factor_out; a.info = info;
-    return dispatch_step_rows<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
-}
-
-// One Newton direction with a dense stage cost C, with or without state box rows (x_lo, x_hi both null: none) and general
-// rows (G, h both null with m == 0: none): the team kernel only, no workspace; with rows the LDS image grows by the hand-over
-// region like alqp_newton_step_rows'.
-template <typename real>
-int newton_step_dense_impl(const AlqpDims *dims, const void *z, const void *xnext, const void *F, const void *x0,
-                           const void *lam, const void *rho, const void *C, const void *q, const void *u_lo,
-                           const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi, long sb_x,
-                           long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h,
-                           void *d_out, void *g_out, void *factor_out, int *info, void *stream) {
-    if (!dims_ok(dims) || !z || !xnext || !F || !x0 || !lam || !rho || !C || !q || !u_lo || !u_hi || !d_out)
-        return ALQP_E_BADARG;
-    if (!x_lo != !x_hi || sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
-    if (!G != !h || (G ? (m < 1 || m > 64) : m != 0) || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0)
-        return ALQP_E_BADARG;
+    if ((kXbox ? (!x_lo || !x_hi) : (!x_lo != !x_hi)) || sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
+    if constexpr (!kXbox) {
+        if (kDense ? (!G != !h || (G ? (m < 1 || m > 64) : m != 0)) : (!G || !h || m < 1 || m > 64)) return ALQP_E_BADARG;
+        if (sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) return ALQP_E_BADARG;
+    }
     const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
     if (img == 0) return ALQP_E_UNSUPPORTED;
     const size_t lds = img + (G ? (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real) : 0);
     if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
-    DenseStepArgs<real> a = {};
+    Args a = {};
     a.B = dims->B; a.T = dims->T;
     a.z = (const real *)z; a.xnext = (const real *)xnext; a.F = (const real *)F; a.x0 = (const real *)x0;
-    a.lam = (const real *)lam; a.rho = (const real *)rho; a.C = (const real *)C; a.q = (const real *)q;
+    a.lam = (const real *)lam; a.rho = (const real *)rho; a.q = (const real *)q;
     a.ulo = (const real *)u_lo; a.uhi = (const real *)u_hi; a.sb_u = sb_u; a.st_u = st_u;
     a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
-    a.G = (const real *)G; a.h = (const real *)h; a.m = m;
-    a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
     a.d_out = (real *)d_out; a.g_out = (real *)g_out; a.factor = (real *)factor_out; a.info = info;
-    if (G) return dispatch_step_dense<real, true>(dims->nx, dims->nu, a, (hipStream_t)stream);
-    return dispatch_step_dense<real, false>(dims->nx, dims->nu, a, (hipStream_t)stream);
+    if constexpr (kDense) a.C = (const real *)cost;
+    else a.Qd = (const real *)cost;
+    if constexpr (kXbox) {
+        return dispatch_step_xbox<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
+    } else {
+        a.G = (const real *)G; a.h = (const real *)h; a.m = m;
+        a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
+        if constexpr (!kDense) return dispatch_step_rows<real>(dims->nx, dims->nu, a, (hipStream_t)stream);
+        else if (G) return dispatch_step_dense<real, true>(dims->nx, dims->nu, a, (hipStream_t)stream);
+        else return dispatch_step_dense<real, false>(dims->nx, dims->nu, a, (hipStream_t)stream);
+    }
 }
+
 
 // fills what the plain and the DYN backward share and launches: quad kernels on a workspace, team kernels on a factor
 template <typename real, bool DYN>
@@ -637,9 +602,9 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                     const void *u_hi, long sb_u, long st_u, const void *x_lo,         \
                                     const void *x_hi, long sb_x, long st_x, void *d_out, void *g_out, \
                                     void *factor_out, int *info, void *stream) {                      \
-        return alqp::newton_step_xbox_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi,  \
-                                                 sb_u, st_u, x_lo, x_hi, sb_x, st_x, d_out, g_out,    \
-                                                 factor_out, info, stream);                           \
+        return alqp::newton_step_ext_impl<REAL, alqp::XboxStepArgs<REAL>>(                            \
+            dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x,   \
+            nullptr, nullptr, 0, 0, 0, 0, 0, d_out, g_out, factor_out, info, stream);                 \
     }                                                                                                 \
     int alqp_newton_step_rows_##SFX(const AlqpDims *dims, const void *z, const void *xnext,           \
                                     const void *F, const void *x0, const void *lam, const void *rho,  \
@@ -649,10 +614,9 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                     const void *h, int m, long sb_g, long st_g, long sb_h, long st_h, \
                                     void *d_out, void *g_out, void *factor_out, int *info,            \
                                     void *stream) {                                                   \
-        return alqp::newton_step_rows_impl<REAL>(dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi,  \
-                                                 sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g,   \
-                                                 st_g, sb_h, st_h, d_out, g_out, factor_out, info,    \
-                                                 stream);                                             \
+        return alqp::newton_step_ext_impl<REAL, alqp::RowsStepArgs<REAL>>(                            \
+            dims, z, xnext, F, x0, lam, rho, Qd, q, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x,   \
+            G, h, m, sb_g, st_g, sb_h, st_h, d_out, g_out, factor_out, info, stream);                 \
     }                                                                                                 \
     int alqp_newton_step_dense_##SFX(const AlqpDims *dims, const void *z, const void *xnext,          \
                                      const void *F, const void *x0, const void *lam, const void *rho, \
@@ -662,10 +626,9 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                      const void *h, int m, long sb_g, long st_g, long sb_h,           \
                                      long st_h, void *d_out, void *g_out, void *factor_out,           \
                                      int *info, void *stream) {                                       \
-        return alqp::newton_step_dense_impl<REAL>(dims, z, xnext, F, x0, lam, rho, C, q, u_lo, u_hi,  \
-                                                  sb_u, st_u, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g,  \
-                                                  st_g, sb_h, st_h, d_out, g_out, factor_out, info,   \
-                                                  stream);                                            \
+        return alqp::newton_step_ext_impl<REAL, alqp::DenseStepArgs<REAL>>(                           \
+            dims, z, xnext, F, x0, lam, rho, C, q, u_lo, u_hi, sb_u, st_u, x_lo, x_hi, sb_x, st_x,    \
+            G, h, m, sb_g, st_g, sb_h, st_h, d_out, g_out, factor_out, info, stream);                 \
     }                                                                                                 \
     int alqp_backward_##SFX(const AlqpDims *dims, const void *factor, void *workspace,                \
                             size_t ws_bytes, const void *F, const void *rho, const void *z_final,     \

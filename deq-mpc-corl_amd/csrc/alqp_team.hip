@@ -334,121 +334,29 @@ __global__ __launch_bounds__(64) void k_newton_step(StepArgs<real> a) {
     }
 }
 
-#ifdef ALQP_XBOX_UNIT
-// The same with state box rows (the state-bound unit only): k_newton_step's body over Team<.., XBOX>, the bounds at
-// gxlo / gxhi, multipliers per stage [u | x] (M = T nx + T (2 nu + 2 nx) per instance). No obstacle rows and no
-// state-estimator row set: forward_sweep's obstacle offset is written without XR.
+#if defined(ALQP_XBOX_UNIT) || defined(ALQP_ROWS_STEP_UNIT) || defined(ALQP_DENSE_STEP_UNIT)
+// The same with more rows per stage and / or a dense stage cost: k_newton_step's statements over Team<.., DENSE, XBOX, POLY>.
+// Three kernels, each in a unit of its own, and like the fused solve above three headers over one body (a shared device
+// function does not keep their register allocation either: profiles/r18/README.md). The members only some of the argument
+// types have (Qd, C, G, h, m) are touched inside `if constexpr`.
+// XBOX: state box rows, the bounds at gxlo / gxhi. POLY: general rows G_t z_t <= h_t, and the LDS image is the team image plus
+// the hand-over region of 2 pad4(m) words per team, set up as k_solve_lin_poly sets it up. DENSE: stage cost
+// 1/2 z_t' C_t z_t + q_t' z_t with C at a.C ([B][T][N][N]) and no gQd. Multipliers per stage [u | (x) | (G)],
+// M = T nx + T (2 nu + (XBOX ? 2 nx : 0) + (POLY ? m : 0)) per instance. No obstacle rows and no state-estimator row set:
+// forward_sweep's obstacle offset is written without XR.
+#if defined(ALQP_XBOX_UNIT)   // the state-bound unit: state box rows
 template <typename real, int NX, int NU>
 __global__ __launch_bounds__(64) void k_newton_step_xbox(XboxStepArgs<real> a) {
-    using C = Cfg<real, NX, NU>;
-    constexpr int G = C::G, N = C::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    real *smem = reinterpret_cast<real *>(smem_raw);
-    const int lane = threadIdx.x, team = lane / G, li = lane % G;
-    const int b_raw = blockIdx.x * C::QPW + team;
-    const bool active = b_raw < a.B;
-    const int b = active ? b_raw : a.B - 1;
-    const int T = a.T;
-    const size_t M = (size_t)C::M(T) + (size_t)2 * T * NX;
-
-    Team<real, NX, NU, false, true> tm;
-    tm.init(smem + (size_t)team * C::team_words(T) + opaque_zero(), li, team * G, T, b);
-    tm.gQd = a.Qd + (size_t)b * T * N;
-    tm.gq = a.q + (size_t)b * T * N;
-    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
-    tm.gc = nullptr;
-    tm.gx0 = a.x0 + (size_t)b * NX;
-    tm.gulo = a.ulo + (size_t)b * a.sb_u;
-    tm.guhi = a.uhi + (size_t)b * a.sb_u;
-    tm.st_u = a.st_u;
-    tm.gxlo = a.xlo + (size_t)b * a.sb_x;
-    tm.gxhi = a.xhi + (size_t)b * a.sb_x;
-    tm.st_x = a.st_x;
-    tm.gxnext = a.xnext + (size_t)b * (T - 1) * NX;
-    const real *gz = a.z + (size_t)b * T * N;
-    tm.lams = const_cast<real *>(a.lam) + (size_t)b * M;  // read-only here
-    for (int e = li; e < T * N; e += G) tm.zs[e] = gz[e];
-    tm.rho = a.rho[b];
-    wave_sync();
-    tm.forward_sweep((active && a.g_out) ? a.g_out + (size_t)b * T * N : nullptr);
-    tm.backward_sweep();
-    if (active) {
-        real *gd = a.d_out + (size_t)b * T * N;
-        for (int e = li; e < T * N; e += G) gd[e] = tm.ds[e];
-        if (a.factor) {
-            real *gf = a.factor + (size_t)b * T * C::XT;
-            for (int e = li; e < T * C::XT; e += G) gf[e] = tm.Xp[e];
-        }
-        if (li == 0 && a.info && tm.info && a.info[b] == 0) a.info[b] = tm.info;
-    }
-}
-#endif
-
-#ifdef ALQP_ROWS_STEP_UNIT
-// The same with general rows G_t z_t <= h_t (the row-step unit only), with (XBOX) or without state box rows: k_newton_step_xbox's
-// body over Team<.., XBOX, POLY>. Multipliers per stage [u | (x) | G] (M = T nx + T (2 nu + (XBOX ? 2 nx : 0) + m) per
-// instance), LDS image the team image plus the hand-over region of 2 pad4(m) words per team, set up as k_solve_lin_poly sets
-// it up. No obstacle rows and no state-estimator row set.
+    constexpr bool DENSE = false, XBOX = true, POLY = false;
+#elif defined(ALQP_ROWS_STEP_UNIT)   // the row-step unit: general rows, with or without state box rows
 template <typename real, int NX, int NU, bool XBOX>
 __global__ __launch_bounds__(64, 1) void k_newton_step_rows(RowsStepArgs<real> a) {
-    using C = Cfg<real, NX, NU>;
-    constexpr int G = C::G, N = C::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    real *smem = reinterpret_cast<real *>(smem_raw);
-    const int lane = threadIdx.x, team = lane / G, li = lane % G;
-    const int b_raw = blockIdx.x * C::QPW + team;
-    const bool active = b_raw < a.B;
-    const int b = active ? b_raw : a.B - 1;
-    const int T = a.T;
-    const size_t M = (size_t)C::M(T) + (XBOX ? (size_t)2 * T * NX : 0) + (size_t)T * a.m;
-    const int team_words = C::team_words(T) + 2 * pad4(a.m);   // the team image, then the hand-over region
-
-    Team<real, NX, NU, false, XBOX, true> tm;
-    tm.init(smem + (size_t)team * team_words + opaque_zero(), li, team * G, T, b);
-    tm.gQd = a.Qd + (size_t)b * T * N;
-    tm.gq = a.q + (size_t)b * T * N;
-    tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
-    tm.gc = nullptr;
-    tm.gx0 = a.x0 + (size_t)b * NX;
-    tm.gulo = a.ulo + (size_t)b * a.sb_u;
-    tm.guhi = a.uhi + (size_t)b * a.sb_u;
-    tm.st_u = a.st_u;
-    if constexpr (XBOX) {
-        tm.gxlo = a.xlo + (size_t)b * a.sb_x;
-        tm.gxhi = a.xhi + (size_t)b * a.sb_x;
-        tm.st_x = a.st_x;
-    }
-    tm.gG = a.G + (size_t)b * a.sb_g;
-    tm.gh = a.h + (size_t)b * a.sb_h;
-    tm.st_g = a.st_g; tm.st_h = a.st_h; tm.pm = a.m;
-    tm.ps = tm.Xp + pad4(T * C::XT);
-    tm.gxnext = a.xnext + (size_t)b * (T - 1) * NX;
-    const real *gz = a.z + (size_t)b * T * N;
-    tm.lams = const_cast<real *>(a.lam) + (size_t)b * M;  // read-only here
-    for (int e = li; e < T * N; e += G) tm.zs[e] = gz[e];
-    tm.rho = a.rho[b];
-    wave_sync();
-    tm.forward_sweep((active && a.g_out) ? a.g_out + (size_t)b * T * N : nullptr);
-    tm.backward_sweep();
-    if (active) {
-        real *gd = a.d_out + (size_t)b * T * N;
-        for (int e = li; e < T * N; e += G) gd[e] = tm.ds[e];
-        if (a.factor) {
-            real *gf = a.factor + (size_t)b * T * C::XT;
-            for (int e = li; e < T * C::XT; e += G) gf[e] = tm.Xp[e];
-        }
-        if (li == 0 && a.info && tm.info && a.info[b] == 0) a.info[b] = tm.info;
-    }
-}
-#endif
-
-#ifdef ALQP_DENSE_STEP_UNIT
-// The same with a dense stage cost 1/2 z_t' C_t z_t + q_t' z_t (the dense-step units only), alone or with state box rows
-// (XBOX) and / or general rows (POLY): k_newton_step_rows' body over Team<.., true, XBOX, POLY>, C at a.C ([B][T][N][N]) and no
-// gQd. Multipliers per stage [u | (x) | (G)], M = T nx + T (2 nu + (XBOX ? 2 nx : 0) + (POLY ? m : 0)) per instance; with POLY
-// the LDS image grows by the hand-over region of 2 pad4(m) words per team. No obstacle rows and no state-estimator row set.
+    constexpr bool DENSE = false, POLY = true;
+#else   // the dense-step units: a dense cost, alone or with state box rows and / or general rows
 template <typename real, int NX, int NU, bool XBOX, bool POLY>
 __global__ __launch_bounds__(64, 1) void k_newton_step_dense(DenseStepArgs<real> a) {
+    constexpr bool DENSE = true;
+#endif
     using C = Cfg<real, NX, NU>;
     constexpr int G = C::G, N = C::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -458,12 +366,15 @@ __global__ __launch_bounds__(64, 1) void k_newton_step_dense(DenseStepArgs<real>
     const bool active = b_raw < a.B;
     const int b = active ? b_raw : a.B - 1;
     const int T = a.T;
-    const size_t M = (size_t)C::M(T) + (XBOX ? (size_t)2 * T * NX : 0) + (POLY ? (size_t)T * a.m : 0);
-    const int team_words = C::team_words(T) + (POLY ? 2 * pad4(a.m) : 0);   // the team image, then the hand-over region
+    int m = 0;
+    if constexpr (POLY) m = a.m;
+    const size_t M = (size_t)C::M(T) + (XBOX ? (size_t)2 * T * NX : 0) + (POLY ? (size_t)T * m : 0);
+    const int team_words = C::team_words(T) + (POLY ? 2 * pad4(m) : 0);   // the team image, then the hand-over region
 
-    Team<real, NX, NU, true, XBOX, POLY> tm;
+    Team<real, NX, NU, DENSE, XBOX, POLY> tm;
     tm.init(smem + (size_t)team * team_words + opaque_zero(), li, team * G, T, b);
-    tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
+    if constexpr (DENSE) tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
+    else tm.gQd = a.Qd + (size_t)b * T * N;
     tm.gq = a.q + (size_t)b * T * N;
     tm.gF = a.F + (size_t)b * (T - 1) * NX * N;
     tm.gc = nullptr;

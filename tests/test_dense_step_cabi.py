@@ -122,21 +122,21 @@ def test_backend_checks_c_lam_and_rows():
     Cs = torch.zeros(B, T, n, n)
     width = lambda x, p: T * nx + T * (2 * nu + (2 * nx if x else 0) + (m if p else 0))
     dt = torch.float32
-    assert be._dense_cargs(dims, torch.zeros(B, width(0, 0)), Cs, None, None, dt) == (None, None, 0, 0, None, None, 0, 0, 0, 0, 0)
+    assert be._fam_cargs("dense", dims, torch.zeros(B, width(0, 0)), Cs, None, None, dt) == (None, None, 0, 0, None, None, 0, 0, 0, 0, 0)
     with pytest.raises(ValueError, match=r"C has shape .* expected \(3, 4, 3, 3\)"):
-        be._dense_cargs(dims, torch.zeros(B, width(0, 0)), torch.zeros(B, T, n), None, None, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(0, 0)), torch.zeros(B, T, n), None, None, dt)
     with pytest.raises(ValueError, match=f"expected \\[B, {width(0, 0)}\\]"):
-        be._dense_cargs(dims, torch.zeros(B, width(0, 0) - 1), Cs, None, None, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(0, 0) - 1), Cs, None, None, dt)
     with pytest.raises(ValueError, match=f"the state-bound rows need \\[B, {width(1, 0)}\\]"):
-        be._dense_cargs(dims, torch.zeros(B, width(0, 0)), Cs, xb, None, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(0, 0)), Cs, xb, None, dt)
     with pytest.raises(ValueError, match=f"these rows need \\[B, {width(0, 1)}\\]"):
-        be._dense_cargs(dims, torch.zeros(B, width(0, 0)), Cs, None, poly, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(0, 0)), Cs, None, poly, dt)
     with pytest.raises(ValueError, match=f"these rows need \\[B, {width(1, 1)}\\]"):
-        be._dense_cargs(dims, torch.zeros(B, width(0, 1)), Cs, xb, poly, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(0, 1)), Cs, xb, poly, dt)
     with pytest.raises(ValueError, match="x_lower has .* too few for strides"):
-        be._dense_cargs(dims, torch.zeros(B, width(1, 0)), Cs, (lo, hi, T * nx, nx), None, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(1, 0)), Cs, (lo, hi, T * nx, nx), None, dt)
     with pytest.raises(ValueError, match="ineqG has .* too few for strides"):
-        be._dense_cargs(dims, torch.zeros(B, width(0, 1)), Cs, None, (poly[0], poly[1], m, 0, m * n, 0, 0), dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(0, 1)), Cs, None, (poly[0], poly[1], m, 0, m * n, 0, 0), dt)
     # past the checks the first thing asked is a device pointer: CPU tensors are refused there, nothing is launched
     with pytest.raises(RuntimeError, match="no CPU fallback"):
-        be._dense_cargs(dims, torch.zeros(B, width(1, 1)), Cs, xb, poly, dt)
+        be._fam_cargs("dense", dims, torch.zeros(B, width(1, 1)), Cs, xb, poly, dt)

@@ -103,17 +103,17 @@ def test_backend_refuses_a_narrow_lam_and_short_rows():
     poly = (G, h, m, 0, 0, 0, 0)
     dims = (B, T, nx, nu)
     M0, M1 = T * nx + T * (2 * nu + m), T * nx + T * (2 * nu + 2 * nx + m)
-    assert HipBackend._rows_checks(dims, torch.zeros(B, M0), None, poly) == (None, None, 0, 0, *poly)
-    assert HipBackend._rows_checks(dims, torch.zeros(B, M1), (lo, hi, 0, 0), poly) == (lo, hi, 0, 0, *poly)
+    assert HipBackend._row_checks(dims, torch.zeros(B, M0), None, None, poly) == (None, None, 0, 0, *poly)
+    assert HipBackend._row_checks(dims, torch.zeros(B, M1), None, (lo, hi, 0, 0), poly) == (lo, hi, 0, 0, *poly)
     with pytest.raises(ValueError, match=f"these rows need \\[B, {M1}\\]"):
-        HipBackend._rows_checks(dims, torch.zeros(B, M0), (lo, hi, 0, 0), poly)
+        HipBackend._row_checks(dims, torch.zeros(B, M0), None, (lo, hi, 0, 0), poly)
     with pytest.raises(ValueError, match=f"these rows need \\[B, {M0}\\]"):
-        HipBackend._rows_checks(dims, torch.zeros(B, T * nx + 2 * T * nu), None, poly)
+        HipBackend._row_checks(dims, torch.zeros(B, T * nx + 2 * T * nu), None, None, poly)
     with pytest.raises(ValueError, match="ineqG has .* too few for strides"):
-        HipBackend._rows_checks(dims, torch.zeros(B, M0), None, (G, h, m, 0, m * n, 0, 0))
+        HipBackend._row_checks(dims, torch.zeros(B, M0), None, None, (G, h, m, 0, m * n, 0, 0))
     with pytest.raises(ValueError, match="ineqh has .* too few for strides"):
-        HipBackend._rows_checks(dims, torch.zeros(B, M0), None, (G, h, m, 0, 0, T * m, m))
+        HipBackend._row_checks(dims, torch.zeros(B, M0), None, None, (G, h, m, 0, 0, T * m, m))
     with pytest.raises(ValueError, match="x_lower has .* too few for strides"):
-        HipBackend._rows_checks(dims, torch.zeros(B, M1), (lo, hi, T * nx, nx), poly)
+        HipBackend._row_checks(dims, torch.zeros(B, M1), None, (lo, hi, T * nx, nx), poly)
     with pytest.raises(ValueError, match="x_upper is required"):
-        HipBackend._rows_checks(dims, torch.zeros(B, M1), (lo, None, 0, 0), poly)
+        HipBackend._row_checks(dims, torch.zeros(B, M1), None, (lo, None, 0, 0), poly)

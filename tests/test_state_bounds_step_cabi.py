@@ -71,10 +71,10 @@ def test_backend_refuses_a_narrow_lam_and_short_bounds():
     B, T, nx, nu = 3, 4, 2, 1
     M = T * nx + T * (2 * nu + 2 * nx)
     lo, hi = torch.zeros(nx), torch.ones(nx)
-    assert HipBackend._xbox_checks((B, T, nx, nu), torch.zeros(B, M), (lo, hi, 0, 0)) == (lo, hi, 0, 0)
+    assert HipBackend._row_checks((B, T, nx, nu), torch.zeros(B, M), None, (lo, hi, 0, 0), None)[:4] == (lo, hi, 0, 0)
     with pytest.raises(ValueError, match="state-bound rows need"):
-        HipBackend._xbox_checks((B, T, nx, nu), torch.zeros(B, T * nx + 2 * T * nu), (lo, hi, 0, 0))
+        HipBackend._row_checks((B, T, nx, nu), torch.zeros(B, T * nx + 2 * T * nu), None, (lo, hi, 0, 0), None)
     with pytest.raises(ValueError, match="too few for strides"):
-        HipBackend._xbox_checks((B, T, nx, nu), torch.zeros(B, M), (lo, hi, T * nx, nx))
+        HipBackend._row_checks((B, T, nx, nu), torch.zeros(B, M), None, (lo, hi, T * nx, nx), None)
     with pytest.raises(ValueError, match="x_upper is required"):
-        HipBackend._xbox_checks((B, T, nx, nu), torch.zeros(B, M), (lo, None, 0, 0))
+        HipBackend._row_checks((B, T, nx, nu), torch.zeros(B, M), None, (lo, None, 0, 0), None)
