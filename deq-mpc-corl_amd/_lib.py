@@ -73,6 +73,11 @@ _SIGS = {
     # name: (restype, argtypes) ; the f32/f64 pairs share a signature
     "alqp_solve_nonlin": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), C.c_int, C.c_double, _P, _P, _P, _P, _P,
                                     C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    # the same with state box rows and / or general rows (team kernel): x_lo, x_hi, sb_x, st_x and G, h, m, sb_g, st_g, sb_h,
+    # st_h behind the control bounds, factor_out and trace behind status (added under ABI version 17: symbols only)
+    "alqp_solve_nonlin_rows": (C.c_int, [C.POINTER(AlqpDims), C.POINTER(AlqpParams), C.c_int, C.c_double, _P, _P, _P, _P, _P,
+                                         C.c_long, C.c_long, _P, _P, C.c_long, C.c_long, *_ROWS, _P, _P, _P, _P, _P, _P, _P,
+                                         _P, C.POINTER(AlqpTrace), _P, C.c_size_t, _P]),
     "alqp_dyn_pendulum1l": (C.c_int, [C.c_long, _P, _P, C.c_double, _P, _P, _P, _P]),
     "alqp_dyn_cartpole1l": (C.c_int, [C.c_long, _P, _P, C.c_double, _P, _P, _P, _P]),
     "alqp_dyn_cartpole1l_v2": (C.c_int, [C.c_long, _P, _P, C.c_double, _P, _P, _P, _P]),
@@ -154,6 +159,7 @@ _PLAIN = {
     "alqp_workspace_bytes": (C.c_size_t, [C.POINTER(AlqpDims), C.c_int]),
     "alqp_exit_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "alqp_workspace_bytes_nonlin": (C.c_size_t, [C.POINTER(AlqpDims), C.c_int]),
+    "alqp_workspace_bytes_nonlin_rows": (C.c_size_t, [C.POINTER(AlqpDims), C.c_int]),
     "alqp_ipm_workspace_bytes": (C.c_size_t, [C.POINTER(AlqpDims), C.c_int]),
 }
 

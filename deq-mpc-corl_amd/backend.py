@@ -380,6 +380,69 @@ class HipBackend:
         self.last_variant = "quad"
         return True
 
+    def nonlin_rows_workspace_bytes(self, dims, dtype):
+        """alqp_workspace_bytes_nonlin_rows: 0 when no compiled-in model of this (nx, nu) runs on the team route."""
+        return int(self.lib.alqp_workspace_bytes_nonlin_rows(C.byref(_lib.AlqpDims(*dims)), int(dtype == torch.float64)))
+
+    def solve_nonlin_rows(self, dims, dyn_id, dyn_h, Qd, q, x0, ulo, uhi, sb_u, st_u, xbnd, poly, z, lam, rho, phi,
+                          rnorm2=None, info=None, status=None, factor=None, al_iter=2, max_newton=4,
+                          flags=_lib.ALQP_INIT_MERIT | _lib.ALQP_DUAL_UPDATE, rho_scale=10.0, trace=None, skip=None,
+                          workspace=None):
+        """Nonlinear fused solve with state bounds and / or general rows (alqp_solve_nonlin_rows): solve_nonlin's problem,
+        the model `dyn_id` inlined, plus xbnd = (xlo, xhi, sb_x, st_x) and / or poly = (G, h, m, sb_g, st_g, sb_h, st_h) as
+        solve_lin_gen takes them (None: absent; at least one must be given). One launch of the team kernel, any batch.
+        lam is [B, T nx + T (2 nu + [2 nx] + [m])], per stage [u | x | G] behind the equality rows. factor (with
+        ALQP_SAVE_FACTOR): the packed factor of the last executed Newton step, for `backward` together with
+        nonlin_rows_F_view(workspace). workspace: a private one (new_workspace_nonlin_rows) when the linearisation it
+        holds afterwards is needed; default: a cached one."""
+        B, T, nx, nu = dims
+        dt = z.dtype
+        name = "alqp_solve_nonlin_rows_" + _dt(z)
+        if xbnd is None and poly is None:
+            raise ValueError("mi_alqp: solve_nonlin_rows needs state bounds or general rows (the plain problem is solve_nonlin's)")
+        rows = self._row_checks(dims, lam, None, xbnd, poly, "these rows need")
+        need = self.nonlin_rows_workspace_bytes(dims, dt)
+        if need == 0:
+            raise RuntimeError("mi_alqp: nonlinear fused solve with rows not available for these sizes")
+        if workspace is not None:
+            ws = workspace
+            if ws.numel() * ws.element_size() < need:
+                raise ValueError("mi_alqp: workspace too small")
+        else:
+            ws = self._scratch(("nlr", z.device, dt), need // z.element_size(), dt, z.device)
+        skp = _ptr(skip, "skip", torch.float64, True)
+        p = _lib.AlqpParams(al_iter, max_newton, 20, flags, rho_scale, 1, skp.value if skp is not None else None)
+        tr = None
+        if trace is not None:
+            tr = _lib.AlqpTrace(*[
+                (trace[k].data_ptr() if trace.get(k) is not None else None)
+                for k in ("g", "d", "phi", "phi_prev", "k", "accept")])
+        rc = getattr(self.lib, name)(
+            C.byref(_lib.AlqpDims(B, T, nx, nu)), C.byref(p), int(dyn_id), float(dyn_h), _ptr(Qd, "Qd", dt),
+            _ptr(q, "q", dt), _ptr(x0, "x0", dt), _ptr(ulo, "u_lower", dt), _ptr(uhi, "u_upper", dt), sb_u, st_u,
+            *self._rows_cargs(rows, dt), _ptr(z, "z", dt), _ptr(lam, "lam", dt), _ptr(rho, "rho", dt),
+            _ptr(phi, "phi", dt), _ptr(rnorm2, "rnorm2", dt, True), _ptr(info, "info", torch.int32, True),
+            _ptr(status, "status", torch.uint8, True), _ptr(factor, "factor", dt, True),
+            C.byref(tr) if tr is not None else None, _ptr(ws, "workspace", dt), need, _stream())
+        _lib.check(rc, name)
+        self.last_variant = "team"
+        return True
+
+    def new_workspace_nonlin_rows(self, dims, like):
+        """A private workspace for solve_nonlin_rows: per instance F [T-1,nx,n], then xnext [T-1,nx]."""
+        need = self.nonlin_rows_workspace_bytes(dims, like.dtype)
+        if need == 0:
+            raise RuntimeError("mi_alqp: nonlinear fused solve with rows not available for these sizes")
+        return torch.empty(need // like.element_size(), dtype=like.dtype, device=like.device)
+
+    def nonlin_rows_F_view(self, ws, dims):
+        """The F regions of a solve_nonlin_rows workspace as a [B, T-1, nx, n] tensor (a strided view: the linearisation of
+        the last executed Newton step of every instance)."""
+        B, T, nx, nu = dims
+        n = nx + nu
+        per = (T - 1) * nx * (n + 1)
+        return ws[:B * per].view(B, per)[:, :(T - 1) * nx * n].view(B, T - 1, nx, n)
+
     def dyn_pendulum1l(self, x, u, h, want_jac=True):
         """pendulum1l provider (alqp_dyn_pendulum1l): x [K,2], u [K,1], h float or [K(,1)] tensor
         -> xnext [K,2], F [K,2,3] or None."""

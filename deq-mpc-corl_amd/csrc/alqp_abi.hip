@@ -9,6 +9,7 @@
 #include "alqp_quad.hpp"   // QCfg
 #include "alqp_dims.hpp"
 #include "alqp_launch.hpp"
+#include "alqp_team_nl.hpp"   // NlRowsSolveArgs, dispatch_solve_nonlin_rows
 #include "mi_alqp.h"
 
 namespace alqp {
@@ -339,6 +340,62 @@ int solve_nonlin_impl(const AlqpDims *dims, const AlqpParams *prm, int dyn_id, d
     return dispatch_solve_nonlin<real>(dyn_id, dims->nx, dims->nu, a, (real *)workspace, (hipStream_t)stream);
 }
 
+// nonlinear fused solve with state bounds and / or general rows (team kernel, alqp_team_nl.hpp): per instance
+// F[T-1][nx][n], then xnext[T-1][nx]. 0: no compiled-in model has this (nx, nu) on that route.
+template <typename real>
+size_t nonlin_rows_ws_bytes(int nx, int nu, int B, int T) {
+    if (nu != 1 || (nx != 2 && nx != 4)) return 0;   // pendulum1l, cartpole1l / cartpole1l_v2
+    return (size_t)B * (T - 1) * nx * (nx + nu + 1) * sizeof(real);
+}
+
+template <typename real>
+int solve_nonlin_rows_impl(const AlqpDims *dims, const AlqpParams *prm, int dyn_id, double dyn_h, const void *Qd,
+                           const void *q, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                           const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,
+                           long sb_g, long st_g, long sb_h, long st_h, void *z, void *lam, void *rho, void *phi,
+                           void *rnorm2, int *info, unsigned char *status, void *factor_out, const AlqpTrace *trace,
+                           void *workspace, size_t ws_bytes, void *stream) {
+    if (!dims || dims->B <= 0 || dims->T < 2 || dims->nx <= 0 || dims->nu <= 0) return ALQP_E_BADARG;   // (an empty batch too)
+    if (!prm || !Qd || !q || !x0 || !u_lo || !u_hi || !z || !lam || !rho || !phi) return ALQP_E_BADARG;
+    if (!x_lo != !x_hi || !G != !h) return ALQP_E_BADARG;
+    if (!x_lo && !G) return ALQP_E_BADARG;   // the plain row set is alqp_solve_nonlin's
+    if (prm->n_ls != 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
+    if (prm->flags & ALQP_EXIT_IN_KERNEL) return ALQP_E_BADARG;   // no cooperative exit on this route
+    if (x_lo && (sb_x < 0 || st_x < 0)) return ALQP_E_BADARG;
+    if (G ? (m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) : m != 0) return ALQP_E_BADARG;
+    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
+    const size_t need = nonlin_rows_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
+    if (need == 0) return ALQP_E_UNSUPPORTED;
+    if (!workspace || ws_bytes < need) return ALQP_E_BADARG;
+    // the horizon must fit the LDS: the team image, plus the hand-over region of 2 pad4(m) words per team with rows
+    const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
+    if (img == 0) return ALQP_E_UNSUPPORTED;
+    if (img + (G ? (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real) : 0) > kMaxLds) return ALQP_E_UNSUPPORTED;
+    NlRowsSolveArgs<real> a = {};
+    AlqpParams p = *prm;
+    p.flags &= ~ALQP_WS_PRIMED;   // ignored: every launch loads z, lam and rho from the caller's arrays
+    if (!set_solve<real>(dims, &p, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
+        return ALQP_E_BADARG;
+    if (x_lo) { a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x; }
+    if (G) {
+        a.G = (const real *)G; a.h = (const real *)h; a.m = m;
+        a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
+    }
+    a.factor = (real *)factor_out;
+    a.dyn_h = (real)dyn_h;
+    a.ws = (real *)workspace;
+    TraceArgs<real> tr = {};
+    if (trace) {
+        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
+        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
+    }
+    const TraceArgs<real> *trp = trace ? &tr : nullptr;
+    const hipStream_t s = (hipStream_t)stream;
+    if (x_lo && G) return dispatch_solve_nonlin_rows<real, kGenXbox | kGenPoly>(dyn_id, dims->nx, dims->nu, a, trp, s);
+    if (x_lo) return dispatch_solve_nonlin_rows<real, kGenXbox>(dyn_id, dims->nx, dims->nu, a, trp, s);
+    return dispatch_solve_nonlin_rows<real, kGenPoly>(dyn_id, dims->nx, dims->nu, a, trp, s);
+}
+
 // a non-null workspace selects the quad kernels; ALQP_E_* when it cannot hold these dims, else 0
 template <typename real>
 int check_quad_ws(const AlqpDims *dims, size_t ws_bytes) {
@@ -474,6 +531,25 @@ int alqp_solve_nonlin_f64(const AlqpDims *dims, const AlqpParams *prm, int dyn_i
     return alqp::solve_nonlin_impl<double>(dims, prm, dyn_id, dyn_h, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi,
                                            rnorm2, info, status, workspace, ws_bytes, stream);
 }
+
+size_t alqp_workspace_bytes_nonlin_rows(const AlqpDims *dims, int is_f64) {
+    if (!alqp::dims_ok(dims)) return 0;
+    return is_f64 ? alqp::nonlin_rows_ws_bytes<double>(dims->nx, dims->nu, dims->B, dims->T)
+                  : alqp::nonlin_rows_ws_bytes<float>(dims->nx, dims->nu, dims->B, dims->T);
+}
+#define ALQP_DEFINE_NONLIN_ROWS(SFX, REAL)                                                                              \
+    int alqp_solve_nonlin_rows_##SFX(                                                                                   \
+        const AlqpDims *dims, const AlqpParams *prm, int dyn_id, double dyn_h, const void *Qd, const void *q,           \
+        const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u, const void *x_lo, const void *x_hi,   \
+        long sb_x, long st_x, const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h, void *z, \
+        void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,              \
+        const AlqpTrace *trace, void *workspace, size_t ws_bytes, void *stream) {                                       \
+        return alqp::solve_nonlin_rows_impl<REAL>(dims, prm, dyn_id, dyn_h, Qd, q, x0, u_lo, u_hi, sb_u, st_u, x_lo,    \
+                                                  x_hi, sb_x, st_x, G, h, m, sb_g, st_g, sb_h, st_h, z, lam, rho, phi,  \
+                                                  rnorm2, info, status, factor_out, trace, workspace, ws_bytes, stream);\
+    }
+ALQP_DEFINE_NONLIN_ROWS(f32, float)
+ALQP_DEFINE_NONLIN_ROWS(f64, double)
 
 size_t alqp_workspace_bytes(const AlqpDims *dims, int is_f64) {
     if (!alqp::dims_ok(dims)) return 0;

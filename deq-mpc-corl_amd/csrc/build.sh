@@ -33,6 +33,9 @@ alqp_team_gen_dxp  alqp_team.hip      -DALQP_GEN_UNIT=7
 alqp_team_rows_step  alqp_team.hip    -DALQP_ROWS_STEP_UNIT
 alqp_team_dense_step       alqp_team.hip  -DALQP_DENSE_STEP_UNIT=0
 alqp_team_dense_step_rows  alqp_team.hip  -DALQP_DENSE_STEP_UNIT=1
+alqp_team_nl_x     alqp_team_nl.hip   -DALQP_NL_UNIT=2
+alqp_team_nl_p     alqp_team_nl.hip   -DALQP_NL_UNIT=4
+alqp_team_nl_xp    alqp_team_nl.hip   -DALQP_NL_UNIT=6
 alqp_quad_dyn_f32  alqp_quad.hip      -DALQP_QUAD_F32 -DALQP_BWD_DYN_UNIT
 alqp_quad_dyn_f64  alqp_quad.hip      -DALQP_QUAD_F64 -DALQP_BWD_DYN_UNIT
 alqp_quad_shdyn_f32  alqp_quad.hip    -DALQP_QUAD_F32 -DALQP_SHDYN_UNIT

@@ -62,6 +62,12 @@ _NO_DENSE_POLY = ("MPC: ineqG / ineqh with diag_cost=False: no kernel instance t
 _NO_XBOX_POLY = ("MPC: ineqG / ineqh with x_lower / x_upper: no kernel instance takes both; write "
                  "the state box as rows of ineqG (G = [I 0; -I 0], h = [x_upper; -x_lower])")
 
+# Models (fused_id) that take the one-launch route with state bounds / general rows BY DEFAULT: those whose median there is at
+# or below the launch-per-step route's in every row of tools/bench_nonlin_rows.py. Every other compiled-in
+# model takes it with prefer_fused=True only. Measured (profiles/r20/bench_nonlin_rows.jsonl): pendulum1l (1) and cartpole1l (2),
+# 1.0-1.8 ms against 1.8-3.3 ms in every row; cartpole1l_v2 (4) was not timed.
+ROWS_FUSED_DEFAULT_IDS = frozenset({1, 2})
+
 
 def _detach_maybe(t):
     if t is None:
@@ -91,6 +97,7 @@ class _Launcher:
         self.cached_ws = getattr(be, "_workspace", None)   # the quad kernels' cached scratch; None: no quad kernels
         self.has_backward_ws = hasattr(be, "backward_ws")
         self.has_solve_nonlin = hasattr(be, "solve_nonlin")
+        self.rows_fused = False   # set by _run: the compiled-in model's one-launch route with state bounds / general rows
         self.has_solve_lin_shared = hasattr(be, "solve_lin_shared")
         # shdyn: (sb_F, st_F, sb_c, st_c) when F or c is shared by the batch (LinDx(F[T-1,nx,n] | F[nx,n]), f likewise), else
         # None. Shared data stays as given only for the plain problem on a backend that has solve_lin_shared; for a dense
@@ -165,6 +172,10 @@ class _Launcher:
 
     def nonlin(self, info=True, **kw):
         st = self.st
+        if self.xbnd is not None or self.poly is not None:   # the team kernel with the model inlined
+            return self.be.solve_nonlin_rows(self.dims, st.dx.fused_id, st.dx.dt, self.Qd, self.q, *self._x0_bounds,
+                                             self.xbnd, self.poly, st.z, st.lam, st.rho, self.phi,
+                                             info=self.info if info else None, workspace=self.nlws, **self._out, **kw)
         return self.be.solve_nonlin(self.dims, st.dx.fused_id, st.dx.dt, self.Qd, self.q, *self._x0_bounds, st.z, st.lam,
                                     st.rho, self.phi, info=self.info if info else None, workspace=self.nlws,
                                     **self._out, **kw)
@@ -357,8 +368,14 @@ class MPC(Module):
     [u - u_upper | -u + u_lower | x - x_upper | -x + x_lower]. With ``LinDx`` the fused team kernel runs, at any batch.
     With a callable ``dx`` / ``dx_jac`` the PyTorch-dynamics route runs with the state-bound twins of
     its four kernels (``HipBackend.newton_step_xbox``, ``merit_xbox``, ``merit_pick_xbox``, ``dual_update_xbox``): the
-    direction comes from the team kernel at any batch, and a provider with a compiled-in model (``PendulumDynamics``,
-    ...) takes this route too. A backend without ``newton_step_xbox`` raises ``NotImplementedError`` for a callable
+    direction comes from the team kernel at any batch. A provider with a compiled-in model (``Pendulum1lDynamics``,
+    ``Cartpole1lDynamics``, ``Cartpole1lV2Dynamics``) keeps its one launch per call: by default
+    the models in ``ROWS_FUSED_DEFAULT_IDS`` (pendulum1l, cartpole1l), the third with ``prefer_fused=True``. That route
+    is ``HipBackend.solve_nonlin_rows``, the team kernel with the model inlined and state bounds and / or general
+    rows: ``exit_mode="fixed"`` one launch per solve, ``"reference"`` a launch per Newton step with the exit test on
+    the device, gradients w.r.t. ``q``, ``diag(C)`` and ``ineqh`` from the packed factor. ``Cartpole2lDynamics`` (no
+    instance of that kernel), a dense cost and a backend without ``solve_nonlin_rows`` take the launch-per-step
+    route. A backend with neither ``newton_step_xbox`` nor that route raises ``NotImplementedError`` for a callable
     ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``; with ``ineqG`` see below, with
     ``diag_cost=False`` above. The gradients of the route in use stay available (callable ``dx``: ``q`` and
     ``diag(C)``), taken with the active set held fixed.
@@ -371,7 +388,7 @@ class MPC(Module):
     any batch. With a callable ``dx`` / ``dx_jac`` the PyTorch-dynamics route runs with the row twins
     of its four kernels (``HipBackend.newton_step_rows``, ``merit_rows``, ``merit_pick_rows``, ``dual_update_rows``),
     which take the state bounds too when both are given: the direction comes from the team kernel at any batch, a
-    provider with a compiled-in model takes this route, and a backend without ``newton_step_rows`` raises
+    provider with a compiled-in model can take its one-launch route (see above), and a backend without ``newton_step_rows`` raises
     ``NotImplementedError`` for a callable ``dx``. Not with ``linearize_once``, ``state_estimator`` or ``Obstacle_MPC``. The
     gradients above stay available (callable ``dx``: ``q`` and ``diag(C)``), and the solve is also differentiable w.r.t. ``ineqh`` (active set held fixed); an
     ``ineqG`` that requires grad raises ``NotImplementedError``.
@@ -874,6 +891,24 @@ class MPC(Module):
                 and (getattr(dx, "fused_default", True) or self.prefer_fused)
                 and (getattr(dx, "nx", None), getattr(dx, "nu", None)) == (self.n_state, self.n_ctrl))
 
+    def _fused_rows_model(self, st, be, dims, dt):
+        """True when this solve takes the compiled-in model's one-launch route WITH state bounds and / or general rows
+        (HipBackend.solve_nonlin_rows; _fused_model above stays the plain row set's predicate): a
+        compiled-in model of these sizes, one call per solve, a diagonal cost, state bounds and / or general rows present,
+        a backend that has the method (and an instance of the model on that route), and `prefer_fused` or a model whose
+        default this route is (ROWS_FUSED_DEFAULT_IDS, and `fused_default`)."""
+        dx = st.dx
+        if not (st.lin is None and not st.stream_mode and not self._has_extra_rows() and self.diag_cost
+                and (self.x_lower is not None or self.ineqG is not None)
+                and not self.linearize_once and not self.state_estimator
+                and hasattr(be, "solve_nonlin_rows")
+                and getattr(dx, "fused_id", None) is not None
+                and (self.prefer_fused or (getattr(dx, "fused_default", True) and dx.fused_id in ROWS_FUSED_DEFAULT_IDS))
+                and (getattr(dx, "nx", None), getattr(dx, "nu", None)) == (self.n_state, self.n_ctrl)):
+            return False
+        has = getattr(be, "nonlin_rows_workspace_bytes", None)   # 0: the library has no instance of this model there
+        return has is None or has(dims, dt) > 0
+
     # ---- the Newton loop of one AL iteration (NewtonAL.forward, al_utils.py:451-576), per route ----
     def _newton_device_exit(self, L, launch, **step_kw):
         """Reference exit rule without a host round trip per Newton step: the batch-global test
@@ -938,6 +973,20 @@ class MPC(Module):
         # L and F of the last executed Newton step are still in the workspace
         return steps, (L.be.nonlin_F_view(L.nlws, L.dims) if need_grad else None)
 
+    def _rows_F_last(self, L, need_grad):
+        """The linearisation of the last executed Newton step out of the private workspace, as the packed backward reads it."""
+        return L.be.nonlin_rows_F_view(L.nlws, L.dims).contiguous() if need_grad else None
+
+    def _al_iter_fused_rows(self, L, need_grad):
+        """_al_iter_fused's shape on the team kernel with rows: a merit launch, one launch per Newton step (each a no-op
+        once the batch-global exit test on the device has fired), then the dual update launch. The packed factor is
+        written by every launch that executes a Newton step."""
+        if need_grad and L.nlws is None:
+            L.nlws = L.be.new_workspace_nonlin_rows(L.dims, L.st.z)
+        steps = self._newton_device_exit(L, L.nonlin, flags=L.save_flag, factor=L.factor)
+        L.nonlin(al_iter=1, max_newton=0, flags=_abi.ALQP_DUAL_UPDATE, info=False)
+        return steps, self._rows_F_last(L, need_grad)
+
     def _al_iter_coop(self, L, need_grad):
         """Affine data, reference exit: starting merit, Newton loop with the batch-global exit and dual update in one
         cooperative launch. None (nothing launched) when the grid cannot be co-resident."""
@@ -998,6 +1047,15 @@ class MPC(Module):
         npa = list(counts.unbind()) if coop else [MAX_NEWTON] * self.al_iter
         return npa, L.st.rho / RHO_SCALE, (L.be.nonlin_F_view(L.nlws, L.dims) if need_grad else None)
 
+    def _solve_fused_rows_one_launch(self, L, need_grad):
+        """Compiled-in model with state bounds and / or general rows, fixed exit: the whole nonlinear solve in ONE launch
+        of the team kernel (no cooperative in-kernel exit on this route)."""
+        if need_grad:   # private workspace: its F regions go with the packed factor
+            L.nlws = L.be.new_workspace_nonlin_rows(L.dims, L.st.z)
+        L.nonlin(al_iter=self.al_iter, max_newton=MAX_NEWTON, factor=L.factor,
+                 flags=_abi.ALQP_INIT_MERIT | _abi.ALQP_DUAL_UPDATE | L.save_flag)
+        return [MAX_NEWTON] * self.al_iter, L.st.rho / RHO_SCALE, self._rows_F_last(L, need_grad)
+
     def _solve_al_loop(self, L, need_grad, fused, coop):
         """The AL outer loop on the host (AL_mpc.py:260-339 / :342-423), one of four bodies per iteration."""
         st, stream = L.st, L.st.stream_mode
@@ -1005,7 +1063,7 @@ class MPC(Module):
         if L.linearize_once:  # dyn_res_clamp_prev starts at the residual of the warm start (:358-369)
             L.merit(st.z, self._true_next(st, st.z))
             prev_mean = self._global_mean(L.rn2.sqrt())
-        body = (self._al_iter_fused if fused else self._al_iter_coop if coop
+        body = (self._al_iter_fused_rows if L.rows_fused else self._al_iter_fused if fused else self._al_iter_coop if coop
                 else self._al_iter_lin if L.F is not None else self._al_iter_torch)
         npa, rho_last, F_last = [], None, None
         for _ in range(100 if L.linearize_once else self.al_iter):
@@ -1044,6 +1102,9 @@ class MPC(Module):
         # a callable dx with a dense cost: the _dense twins of the launch-per-step kernels, which take
         # the state bounds and the general rows too
         dense_step = st.lin is None and hasattr(be, "newton_step_dense")
+        # a compiled-in model on its one-launch route with state bounds / general rows needs none of the
+        # launch-per-step twins the guards below ask a callable dx for
+        rows_fused = self._fused_rows_model(st, be, dims, dt)
         if not hasattr(be, "solve_lin_gen"):
             # (a backend given to the constructor was refused there; this is the lazily resolved default's turn)
             if self.x_lower is not None and not self.diag_cost and not dense_step:
@@ -1069,35 +1130,37 @@ class MPC(Module):
                                           "nonlinear-caller kernels and the compiled-in models read diag(C)")
         if self.x_lower is not None:
             # the state-bound rows live in the fused team kernel (alqp_solve_lin_xbox) and, for a callable dx, in the
-            # launch-per-step kernels' _xbox twins; the quad step kernels, the obstacle /
-            # state-estimator row sets and the compiled-in models know no such rows
+            # launch-per-step kernels' _xbox twins, for a compiled-in model in the team kernel of DESIGN
+            # section 28; the quad step kernels (the quad fused solve of the compiled-in models among them) and the obstacle /
+            # state-estimator row sets know no such rows
             if self._has_extra_rows():
                 raise NotImplementedError("MPC: x_lower / x_upper with obstacle rows (Obstacle_MPC): the state-bound "
                                           "variants of the nonlinear-caller kernels take no obstacle rows")
             if self.linearize_once:
                 raise NotImplementedError("MPC: x_lower / x_upper with linearize_once: the frozen-linearisation route "
                                           "is not built with state-bound rows")
-            if st.lin is None and not (hasattr(be, "newton_step_xbox")
+            if st.lin is None and not (rows_fused or hasattr(be, "newton_step_xbox")
                                        or (self.ineqG is not None and hasattr(be, "newton_step_rows"))
                                        or (not self.diag_cost and dense_step)):
                 raise NotImplementedError("MPC: x_lower / x_upper need affine dynamics given as LinDx(F, f): the "
-                                          "nonlinear-caller kernels and the compiled-in models know no state-bound rows")
+                                          "nonlinear-caller kernels and the compiled-in models know no state-bound rows")   # (wording pinned by tests: the models' quad solve)
             if st.lam.shape[1] != self.neq + self.nineq:
                 raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the state bounds need "
                                  f"{self.neq + self.nineq} = T nx + T (2 nu + 2 nx{' + m' if self.n_rows else ''})")
         if self.ineqG is not None:
             # the general rows live in the fused team kernel (alqp_solve_lin_poly) and, for a callable dx, in the
-            # launch-per-step kernels' _rows twins; the quad step kernels, the obstacle /
-            # state-estimator row sets and the compiled-in models know no such rows
+            # launch-per-step kernels' _rows twins, for a compiled-in model in the team kernel of DESIGN
+            # section 28; the quad step kernels (the quad fused solve of the compiled-in models among them) and the obstacle /
+            # state-estimator row sets know no such rows
             if self._has_extra_rows():
                 raise NotImplementedError("MPC: ineqG / ineqh with obstacle rows (Obstacle_MPC): those run on the "
                                           "nonlinear-caller kernels, which know no general rows")
             if self.linearize_once:
                 raise NotImplementedError("MPC: ineqG / ineqh with linearize_once: the frozen-linearisation route "
                                           "evaluates merit and dual update with kernels that know no general rows")
-            if st.lin is None and not (hasattr(be, "newton_step_rows") or (not self.diag_cost and dense_step)):
+            if st.lin is None and not (rows_fused or hasattr(be, "newton_step_rows") or (not self.diag_cost and dense_step)):
                 raise NotImplementedError("MPC: ineqG / ineqh need affine dynamics given as LinDx(F, f): the "
-                                          "nonlinear-caller kernels and the compiled-in models know no general rows")
+                                          "nonlinear-caller kernels and the compiled-in models know no general rows")   # (wording pinned by tests: the models' quad solve)
             if st.lam.shape[1] != self.neq + self.nineq:
                 raise ValueError(f"MPC: lamda has {st.lam.shape[1]} rows per instance, the general rows need "
                                  f"{self.neq + self.nineq} = T nx + T (2 nu{' + 2 nx' if self.x_lower is not None else ''} + m)")
@@ -1162,11 +1225,14 @@ class MPC(Module):
         fused = L.has_solve_nonlin and self._fused_model(st)
         coop_nl = in_kernel and fused and (self.exit_in_kernel is True or (auto and -(-B // 16) <= 512))
         fixed = self.exit_mode == "fixed"
+        L.rows_fused = rows_fused
         res = None
         if F is not None and not stream and (coop or fixed):
             res = self._solve_lin_one_launch(L, need_grad, coop)
         elif fused and (coop_nl or fixed):
             res = self._solve_fused_one_launch(L, need_grad, coop_nl)
+        elif L.rows_fused and fixed:
+            res = self._solve_fused_rows_one_launch(L, need_grad)
         if res is None:
             res = self._solve_al_loop(L, need_grad, fused, coop)
         npa, rho_last, F_last = res
@@ -1199,7 +1265,7 @@ class MPC(Module):
         if need_grad and F_last is not None:
             if F_last.dim() < 4:   # the backward kernels read a per-instance F: materialised only here, for them
                 F_last = F_last.expand(B, T - 1, nx, n).contiguous()
-            if L.nlws is not None:
+            if L.nlws is not None and not L.rows_fused:
                 return "workspace", L.nlws, F_last, rho_last
             if use_qws:
                 return "workspace", L.qws, F_last, rho_last

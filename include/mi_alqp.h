@@ -636,6 +636,48 @@ int alqp_solve_nonlin_f64(const AlqpDims *dims, const AlqpParams *prm, int dyn_i
                           void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * The nonlinear fused solve with state box rows and / or general rows (ABI 17, symbols added: detect them by lookup):
+ * alqp_solve_nonlin's problem plus xlo[t] <= x_t <= xhi[t] and / or G_t z_t <= h_t on every stage, in ONE launch of a
+ * team kernel (one lane team per instance, factor in LDS). dyn_id 1 (pendulum1l), 2 (cartpole1l)
+ * and 4 (cartpole1l_v2); 3 (cartpole2l) has no instance on this route (ALQP_E_UNSUPPORTED: its builds spill registers).
+ * x_lo / x_hi, sb_x, st_x as alqp_solve_lin_xbox takes them, both NULL: no state bounds. G, h, m and their strides as
+ * alqp_solve_lin_poly takes them, both NULL and m == 0: no general rows. Every bound and every entry of G and h must be
+ * finite (the host encodes "no bound" / "no row" as a value that is never active). lam is [B][M],
+ * M = T nx + T (2 nu + [2 nx] + [m]), per stage [u - u_hi | -u + u_lo | x - x_hi | -x + x_lo | G_t z_t - h_t] behind the
+ * equality rows, as alqp_solve_lin_gen's.
+ * Per AL iteration: with ALQP_INIT_MERIT the merit at z with the true dynamics; max_newton times (linearise at z with
+ * the model, Newton direction on that linearisation, the 20 candidate merits with the TRUE dynamics, first argmin,
+ * accept iff below the previous merit); the true residual at the iterate the iteration ends on; with ALQP_DUAL_UPDATE
+ * the dual update on that residual and rho *= rho_scale. Outputs, info (sticky), status, rnorm2 and trace as
+ * alqp_solve_lin_*; factor_out (ALQP_SAVE_FACTOR) receives the packed factor of the last Newton step of a launch that
+ * executes one, for alqp_backward_* together with the F region of the workspace.
+ * workspace: alqp_workspace_bytes_nonlin_rows() bytes (0: no model of that (nx, nu) on this route), [B] times
+ * (F[T-1][nx][n], then xnext[T-1][nx]). Its prior contents are never read before they are written. Launches with
+ * max_newton == 0 (merit only, dual update only) and the end of every AL iteration write ONLY the xnext part: the F part
+ * keeps the linearisation of the last executed Newton step.
+ * n_ls must be 20. ALQP_INIT_MERIT, ALQP_DUAL_UPDATE, ALQP_SAVE_FACTOR and skip_flag as in alqp_solve_lin_*;
+ * ALQP_WS_PRIMED is ignored; AlqpParams.variant is not read.
+ * ALQP_E_BADARG: neither row family given, one half of a pair null, m outside 1..64 with rows (or m != 0 without), a
+ * negative stride, an empty batch, n_ls != 20, a null or too small workspace, ALQP_EXIT_IN_KERNEL (this route has no
+ * cooperative exit), ALQP_SAVE_FACTOR without factor_out. ALQP_E_UNSUPPORTED: an unknown dyn_id or one without an
+ * instance here, an (nx, nu) that is not the model's, a horizon (or m) whose LDS image (the team image, with general rows
+ * plus 2 pad4(m) words per team) does not fit.
+ */
+size_t alqp_workspace_bytes_nonlin_rows(const AlqpDims *dims, int is_f64);
+int alqp_solve_nonlin_rows_f32(const AlqpDims *dims, const AlqpParams *prm, int dyn_id, double dyn_h, const void *Qd,
+                               const void *q, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                               const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h,
+                               int m, long sb_g, long st_g, long sb_h, long st_h, void *z, void *lam, void *rho,
+                               void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,
+                               const AlqpTrace *trace, void *workspace, size_t ws_bytes, void *stream);
+int alqp_solve_nonlin_rows_f64(const AlqpDims *dims, const AlqpParams *prm, int dyn_id, double dyn_h, const void *Qd,
+                               const void *q, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
+                               const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h,
+                               int m, long sb_g, long st_g, long sb_h, long st_h, void *z, void *lam, void *rho,
+                               void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,
+                               const AlqpTrace *trace, void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * ---- Obstacle inequalities (Obstacle_MPC, qpth/AL_mpc_custom.py:22-135; al_utils.py:313-323, 351-388) ----
  * `nobs` spheres per stage add the rows  c_k = radius^2 - |x_t[0:3] - pos_k|^2 <= 0  behind the stage's
  * 2 nu bound rows: lam [B][M], M = T*nx + T*(2*nu + nobs), inequality row T*nx + t*(2*nu + nobs) + j with
