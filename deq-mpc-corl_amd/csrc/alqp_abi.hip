@@ -81,6 +81,17 @@ int pick_variant(const AlqpDims *dims, int flags, long quad_min_batch) {
     return (dims->B >= qmin || team_lds > kMaxLds) ? 2 : 1;
 }
 
+// The nullable AlqpTrace of the C ABI -> the kernels' TraceArgs (all null without one).
+template <typename real>
+TraceArgs<real> trace_args(const AlqpTrace *trace) {
+    TraceArgs<real> tr = {};
+    if (trace) {
+        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
+        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
+    }
+    return tr;
+}
+
 // The SolveArgs fields that alqp_solve_lin and alqp_solve_nonlin fill alike; F, c, factor, stagger and dyn_h are the
 // caller's. false: ALQP_EXIT_IN_KERNEL without its scratch or together with a skip flag (ALQP_E_BADARG).
 template <typename real>
@@ -122,11 +133,7 @@ int solve_lin_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, 
         return ALQP_E_BADARG;
     a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
     a.stagger = quad_stagger(prm->quad_stagger, dims->B, dims->T, dims->nx, dims->nu, prm->al_iter * prm->max_newton, sizeof(real) == 8);
-    TraceArgs<real> tr = {};
-    if (trace) {
-        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
-        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
-    }
+    const TraceArgs<real> tr = trace_args<real>(trace);
     // variant: 1 = team (factor in LDS), 2 = quad (4 lanes/instance, HBM workspace), 0 = auto
     const size_t need = quad_ws_bytes<real>(dims->nx, dims->nu, dims->B, dims->T);
     int variant = prm->variant;
@@ -169,111 +176,23 @@ int solve_lin_shared_impl(const AlqpDims *dims, const AlqpParams *prm, const voi
                                                       a, dispatch_solve_shdyn<real>, dispatch_solve_quad_shdyn<real>);
 }
 
-// Dense stage cost: the team kernel only (no quad kernel reads a full C), so no workspace and variant 0 / 1 alike.
+// Dense stage cost (C), state box rows (x_lo, x_hi) and general rows G_t z_t <= h_t (G, h, m), any non-empty set of them:
+// the non-null set is the mask that picks the object (build.sh, alqp_team_gen_*), and `accept` holds bit (1 << mask) for
+// every mask the calling entry point takes (alqp_solve_lin_dense_* / _xbox_* / _poly_*: its own feature alone;
+// alqp_solve_lin_gen_*: two or three). The team kernel only: no quad kernel reads a full C or knows such rows, so no
+// workspace and variant 0 / 1 alike. Qd is ignored with a C.
 template <typename real>
-int solve_lin_dense_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Cm, const void *q, const void *F,
-                         const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
-                         void *z, void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
-                         void *factor_out, const AlqpTrace *trace, void *stream) {
-    if (!dims_ok(dims) || !prm || !Cm || !q || !F || !c || !x0 || !u_lo || !u_hi || !z || !lam || !rho || !phi)
-        return ALQP_E_BADARG;
-    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
-    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
-    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
-    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
-    DenseSolveArgs<real> a = {};
-    if (!set_solve<real>(dims, prm, nullptr, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
-        return ALQP_E_BADARG;
-    a.C = (const real *)Cm;
-    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
-    TraceArgs<real> tr = {};
-    if (trace) {
-        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
-        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
-    }
-    return dispatch_solve_dense<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
-}
-
-// State box rows xlo <= x_t <= xhi: the team kernel only, like the dense cost (the quad kernels know no such rows).
-template <typename real>
-int solve_lin_xbox_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
-                        const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
-                        const void *x_lo, const void *x_hi, long sb_x, long st_x, void *z, void *lam, void *rho,
-                        void *phi, void *rnorm2, int *info, unsigned char *status, void *factor_out,
-                        const AlqpTrace *trace, void *stream) {
-    if (!dims_ok(dims) || !prm || !Qd || !q || !F || !c || !x0 || !u_lo || !u_hi || !x_lo || !x_hi || !z || !lam ||
-        !rho || !phi)
-        return ALQP_E_BADARG;
-    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
-    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
-    if (sb_x < 0 || st_x < 0) return ALQP_E_BADARG;
-    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
-    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
-    // the horizon must fit the team's LDS image (that of the plain kernel): there is no quad kernel to fall back on
-    const size_t lds = lds_query<real>(dims->nx, dims->nu, dims->T);
-    if (lds == 0 || lds > kMaxLds) return ALQP_E_UNSUPPORTED;
-    XboxSolveArgs<real> a = {};
-    if (!set_solve<real>(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
-        return ALQP_E_BADARG;
-    a.xlo = (const real *)x_lo; a.xhi = (const real *)x_hi; a.sb_x = sb_x; a.st_x = st_x;
-    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
-    TraceArgs<real> tr = {};
-    if (trace) {
-        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
-        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
-    }
-    return dispatch_solve_xbox<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
-}
-
-// General rows G_t z_t <= h_t: the team kernel only (the quad kernels know no such rows), no workspace.
-template <typename real>
-int solve_lin_poly_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
-                        const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
-                        const void *G, const void *h, int m, long sb_g, long st_g, long sb_h, long st_h, void *z,
-                        void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
-                        void *factor_out, const AlqpTrace *trace, void *stream) {
-    if (!dims_ok(dims) || !prm || !Qd || !q || !F || !c || !x0 || !u_lo || !u_hi || !G || !h || !z || !lam || !rho ||
-        !phi)
-        return ALQP_E_BADARG;
-    if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
-    if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
-    if (m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0) return ALQP_E_BADARG;
-    if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
-    if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
-    // the horizon must fit the LDS: the team image plus the hand-over region of 2 pad4(m) words per team (there is no
-    // quad kernel to fall back on)
-    const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
-    if (img == 0) return ALQP_E_UNSUPPORTED;
-    const size_t lds = img + (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real);
-    if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
-    PolySolveArgs<real> a = {};
-    if (!set_solve<real>(dims, prm, Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info, status, a))
-        return ALQP_E_BADARG;
-    a.G = (const real *)G; a.h = (const real *)h; a.m = m;
-    a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
-    a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
-    TraceArgs<real> tr = {};
-    if (trace) {
-        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
-        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
-    }
-    return dispatch_solve_poly<real>(dims->nx, dims->nu, a, trace ? &tr : nullptr, (hipStream_t)stream);
-}
-
-// Two or three of dense cost, state bounds and general rows together: the non-null set picks the object (build.sh,
-// alqp_team_gen_*). Team kernel only, like each of them alone.
-template <typename real>
-int solve_lin_gen_impl(const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q, const void *F,
-                       const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u, long st_u,
-                       void *z, void *lam, void *rho, void *phi, void *rnorm2, int *info, unsigned char *status,
-                       void *factor_out, const AlqpTrace *trace, void *stream, const void *Cm, const void *x_lo,
-                       const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m, long sb_g,
-                       long st_g, long sb_h, long st_h) {
+int solve_lin_feat_impl(int accept, const AlqpDims *dims, const AlqpParams *prm, const void *Qd, const void *q,
+                        const void *F, const void *c, const void *x0, const void *u_lo, const void *u_hi, long sb_u,
+                        long st_u, void *z, void *lam, void *rho, void *phi, void *rnorm2, int *info,
+                        unsigned char *status, void *factor_out, const AlqpTrace *trace, void *stream, const void *Cm,
+                        const void *x_lo, const void *x_hi, long sb_x, long st_x, const void *G, const void *h, int m,
+                        long sb_g, long st_g, long sb_h, long st_h) {
     if (!dims_ok(dims) || !prm || !q || !F || !c || !x0 || !u_lo || !u_hi || !z || !lam || !rho || !phi)
         return ALQP_E_BADARG;
     if (!x_lo != !x_hi || !G != !h) return ALQP_E_BADARG;
     const int mask = (Cm ? kGenDense : 0) | (x_lo ? kGenXbox : 0) | (G ? kGenPoly : 0);
-    if (mask != 3 && mask != 5 && mask != 6 && mask != 7) return ALQP_E_BADARG;   // fewer than two features
+    if (!(accept >> mask & 1)) return ALQP_E_BADARG;   // a feature's pointers missing, or not this entry point's set
     if (!Cm && !Qd) return ALQP_E_BADARG;
     if (prm->n_ls < 1 || prm->n_ls > 20 || prm->al_iter < 0 || prm->max_newton < 0) return ALQP_E_BADARG;
     if (prm->variant != 0 && prm->variant != 1) return ALQP_E_BADARG;
@@ -281,11 +200,15 @@ int solve_lin_gen_impl(const AlqpDims *dims, const AlqpParams *prm, const void *
     if (G && (m < 1 || m > 64 || sb_g < 0 || st_g < 0 || sb_h < 0 || st_h < 0)) return ALQP_E_BADARG;
     if ((prm->flags & ALQP_SAVE_FACTOR) && !factor_out) return ALQP_E_BADARG;
     if ((prm->flags & ALQP_EXIT_IN_KERNEL) && trace) return ALQP_E_BADARG;
-    // the horizon must fit the LDS: the team image, plus the hand-over region of 2 pad4(m) words per team with rows
-    const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
-    if (img == 0) return ALQP_E_UNSUPPORTED;
-    const size_t lds = img + (G ? (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real) : 0);
-    if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    // the horizon must fit the LDS: the team image, plus the hand-over region of 2 pad4(m) words per team with rows (there is
+    // no quad kernel to fall back on). Not with the dense cost alone: that entry point has always left this to the launcher,
+    // which answers the same ALQP_E_UNSUPPORTED, but behind set_solve's ALQP_E_BADARG.
+    if (mask != kGenDense) {
+        const size_t img = lds_query<real>(dims->nx, dims->nu, dims->T);
+        if (img == 0) return ALQP_E_UNSUPPORTED;
+        const size_t lds = img + (G ? (size_t)qpw_query(dims->nx, dims->nu) * 2 * pad4(m) * sizeof(real) : 0);
+        if (lds > kMaxLds) return ALQP_E_UNSUPPORTED;
+    }
     GenSolveArgs<real> a = {};
     if (!set_solve<real>(dims, prm, Cm ? nullptr : Qd, q, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi, rnorm2, info,
                          status, a))
@@ -297,20 +220,22 @@ int solve_lin_gen_impl(const AlqpDims *dims, const AlqpParams *prm, const void *
         a.sb_g = sb_g; a.st_g = st_g; a.sb_h = sb_h; a.st_h = st_h;
     }
     a.F = (const real *)F; a.c = (const real *)c; a.factor = (real *)factor_out;
-    TraceArgs<real> tr = {};
-    if (trace) {
-        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
-        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
-    }
+    const TraceArgs<real> tr = trace_args<real>(trace);
     const TraceArgs<real> *trp = trace ? &tr : nullptr;
     const hipStream_t s = (hipStream_t)stream;
     switch (mask) {
-        case kGenDense | kGenXbox: return dispatch_solve_gen<real, kGenDense | kGenXbox>(dims->nx, dims->nu, a, trp, s);
-        case kGenDense | kGenPoly: return dispatch_solve_gen<real, kGenDense | kGenPoly>(dims->nx, dims->nu, a, trp, s);
-        case kGenXbox | kGenPoly: return dispatch_solve_gen<real, kGenXbox | kGenPoly>(dims->nx, dims->nu, a, trp, s);
-        default: return dispatch_solve_gen<real, kGenDense | kGenXbox | kGenPoly>(dims->nx, dims->nu, a, trp, s);
+        case 1: return dispatch_solve_gen<real, 1>(dims->nx, dims->nu, a, trp, s);
+        case 2: return dispatch_solve_gen<real, 2>(dims->nx, dims->nu, a, trp, s);
+        case 3: return dispatch_solve_gen<real, 3>(dims->nx, dims->nu, a, trp, s);
+        case 4: return dispatch_solve_gen<real, 4>(dims->nx, dims->nu, a, trp, s);
+        case 5: return dispatch_solve_gen<real, 5>(dims->nx, dims->nu, a, trp, s);
+        case 6: return dispatch_solve_gen<real, 6>(dims->nx, dims->nu, a, trp, s);
+        default: return dispatch_solve_gen<real, 7>(dims->nx, dims->nu, a, trp, s);
     }
 }
+// the masks an entry point takes, as solve_lin_feat_impl's `accept`
+constexpr int kAcceptDense = 1 << kGenDense, kAcceptXbox = 1 << kGenXbox, kAcceptPoly = 1 << kGenPoly;
+constexpr int kAcceptGen = 1 << 3 | 1 << 5 | 1 << 6 | 1 << 7;   // two or three features
 
 // nonlinear fused solve: workspace = [records | F linearisations [B][T-1][nx][n]]
 template <typename real>
@@ -384,11 +309,7 @@ int solve_nonlin_rows_impl(const AlqpDims *dims, const AlqpParams *prm, int dyn_
     a.factor = (real *)factor_out;
     a.dyn_h = (real)dyn_h;
     a.ws = (real *)workspace;
-    TraceArgs<real> tr = {};
-    if (trace) {
-        tr.g = (real *)trace->g; tr.d = (real *)trace->d; tr.phi = (real *)trace->phi;
-        tr.phi_prev = (real *)trace->phi_prev; tr.k = trace->k; tr.accept = trace->accept;
-    }
+    const TraceArgs<real> tr = trace_args<real>(trace);
     const TraceArgs<real> *trp = trace ? &tr : nullptr;
     const hipStream_t s = (hipStream_t)stream;
     if (x_lo && G) return dispatch_solve_nonlin_rows<real, kGenXbox | kGenPoly>(dyn_id, dims->nx, dims->nu, a, trp, s);
@@ -622,9 +543,10 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                    void *lam, void *rho, void *phi, void *rnorm2, int *info,          \
                                    unsigned char *status, void *factor_out, const AlqpTrace *trace,   \
                                    void *stream) {                                                    \
-        return alqp::solve_lin_dense_impl<REAL>(dims, prm, C, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, \
-                                                lam, rho, phi, rnorm2, info, status, factor_out,      \
-                                                trace, stream);                                       \
+        return alqp::solve_lin_feat_impl<REAL>(                                                       \
+            alqp::kAcceptDense, dims, prm, nullptr, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, \
+            phi, rnorm2, info, status, factor_out, trace, stream, C, nullptr, nullptr, 0, 0, nullptr, \
+            nullptr, 0, 0, 0, 0, 0);                                                                  \
     }                                                                                                 \
     int alqp_solve_lin_xbox_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,        \
                                   const void *q, const void *F, const void *c, const void *x0,        \
@@ -633,9 +555,10 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                   void *lam, void *rho, void *phi, void *rnorm2, int *info,           \
                                   unsigned char *status, void *factor_out, const AlqpTrace *trace,    \
                                   void *stream) {                                                     \
-        return alqp::solve_lin_xbox_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u,    \
-                                               x_lo, x_hi, sb_x, st_x, z, lam, rho, phi, rnorm2,      \
-                                               info, status, factor_out, trace, stream);              \
+        return alqp::solve_lin_feat_impl<REAL>(                                                       \
+            alqp::kAcceptXbox, dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi,  \
+            rnorm2, info, status, factor_out, trace, stream, nullptr, x_lo, x_hi, sb_x, st_x,         \
+            nullptr, nullptr, 0, 0, 0, 0, 0);                                                         \
     }                                                                                                 \
     int alqp_solve_lin_poly_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,        \
                                   const void *q, const void *F, const void *c, const void *x0,        \
@@ -644,9 +567,10 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                   long sb_h, long st_h, void *z, void *lam, void *rho, void *phi,     \
                                   void *rnorm2, int *info, unsigned char *status, void *factor_out,   \
                                   const AlqpTrace *trace, void *stream) {                             \
-        return alqp::solve_lin_poly_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u,    \
-                                               G, h, m, sb_g, st_g, sb_h, st_h, z, lam, rho, phi,     \
-                                               rnorm2, info, status, factor_out, trace, stream);      \
+        return alqp::solve_lin_feat_impl<REAL>(                                                       \
+            alqp::kAcceptPoly, dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi,  \
+            rnorm2, info, status, factor_out, trace, stream, nullptr, nullptr, nullptr, 0, 0, G, h,   \
+            m, sb_g, st_g, sb_h, st_h);                                                               \
     }                                                                                                 \
     int alqp_solve_lin_gen_##SFX(const AlqpDims *dims, const AlqpParams *prm, const void *Qd,         \
                                  const void *q, const void *F, const void *c, const void *x0,         \
@@ -658,10 +582,10 @@ int alqp_qps_per_wave(const AlqpDims *dims, int is_f64) {
                                  const void *G, const void *h, int m, long sb_g, long st_g,           \
                                  long sb_h, long st_h) {                                              \
         (void)workspace; (void)ws_bytes;                                                              \
-        return alqp::solve_lin_gen_impl<REAL>(dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z,  \
-                                              lam, rho, phi, rnorm2, info, status, factor_out, trace, \
-                                              stream, C, x_lo, x_hi, sb_x, st_x, G, h, m, sb_g, st_g, \
-                                              sb_h, st_h);                                            \
+        return alqp::solve_lin_feat_impl<REAL>(                                                       \
+            alqp::kAcceptGen, dims, prm, Qd, q, F, c, x0, u_lo, u_hi, sb_u, st_u, z, lam, rho, phi,   \
+            rnorm2, info, status, factor_out, trace, stream, C, x_lo, x_hi, sb_x, st_x, G, h, m,      \
+            sb_g, st_g, sb_h, st_h);                                                                  \
     }                                                                                                 \
     int alqp_newton_step_##SFX(const AlqpDims *dims, const void *z, const void *xnext, const void *F, \
                                const void *x0, const void *lam, const void *rho, const void *Qd,      \

@@ -27,40 +27,18 @@ struct SolveArgs {
     double *exit_scratch;  // arrival counter, then [2][gridDim.x] per-workgroup partial sums (ping-pong), then a time-out flag
 };
 
-// The dense-cost fused solve (k_solve_lin_dense): the stage cost's full matrices behind the plain arguments, in a type of
-// its own so that SolveArgs, and with it the plain kernels' argument block, stays what it was. Qd is unused.
-template <typename real>
-struct DenseSolveArgs : SolveArgs<real> {
-    const real *C;   // [B][T][n][n] row-major, symmetric
-};
-
-// The state-bound fused solve (k_solve_lin_xbox): the state box bounds behind the plain arguments, again in a type of its own.
-template <typename real>
-struct XboxSolveArgs : SolveArgs<real> {
-    const real *xlo, *xhi;   // [nx] (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx)
-    long sb_x, st_x;         // words from one instance's / one stage's bounds to the next
-};
-
-// The fused solve with stage-wise linear rows G_t z_t <= h_t (k_solve_lin_poly): the rows behind the plain arguments, again
-// in a type of its own.
-template <typename real>
-struct PolySolveArgs : SolveArgs<real> {
-    const real *G, *h;   // G: [m][n] (sb_g = st_g = 0), [T][m][n] (0, m n) or [B][T][m][n] (T m n, m n); h likewise without [n]
-    int m;               // rows per stage, 1 .. 64
-    long sb_g, st_g;     // words from one instance's / one stage's G to the next
-    long sb_h, st_h;
-};
-
-// The fused solve with two or three of the above together (k_solve_lin_gen<.., DENSE, XBOX, POLY, ..>): every member of the
-// three structs above behind the plain arguments; an instantiation reads those of its flags (Qd only without DENSE).
+// The fused solve with a dense stage cost, state box rows and / or stage-wise linear rows G_t z_t <= h_t
+// (k_solve_lin_gen<.., DENSE, XBOX, POLY, ..>): every feature's arguments behind the plain ones, in a type of its own so that
+// SolveArgs, and with it the plain kernels' argument block, stays what it was. An instantiation reads the members of its
+// flags (Qd only without DENSE).
 template <typename real>
 struct GenSolveArgs : SolveArgs<real> {
-    const real *C;
-    const real *xlo, *xhi;
-    long sb_x, st_x;
-    const real *G, *h;
-    int m;
-    long sb_g, st_g;
+    const real *C;           // DENSE: [B][T][n][n] row-major, symmetric
+    const real *xlo, *xhi;   // XBOX: [nx] (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx)
+    long sb_x, st_x;         // words from one instance's / one stage's bounds to the next
+    const real *G, *h;       // POLY: G [m][n] (sb_g = st_g = 0), [T][m][n] (0, m n) or [B][T][m][n] (T m n, m n); h likewise without [n]
+    int m;                   // rows per stage, 1 .. 64
+    long sb_g, st_g;         // words from one instance's / one stage's G to the next
     long sb_h, st_h;
 };
 
@@ -168,7 +146,7 @@ struct StepArgs {
 };
 
 // The one-step kernel with state box rows (k_newton_step_xbox): the bounds behind the plain arguments, in a type of its own
-// like XboxSolveArgs, so that StepArgs and k_newton_step stay what they were. obs / nobs / obs_r2 / no_init are unused (0).
+// like GenSolveArgs, so that StepArgs and k_newton_step stay what they were. obs / nobs / obs_r2 / no_init are unused (0).
 template <typename real>
 struct XboxStepArgs : StepArgs<real> {
     const real *xlo, *xhi;   // [nx] (sb_x = st_x = 0) or [B][T][nx] (sb_x = T nx, st_x = nx)
@@ -176,7 +154,7 @@ struct XboxStepArgs : StepArgs<real> {
 };
 
 // The one-step kernel with general rows G_t z_t <= h_t (k_newton_step_rows<.., XBOX>): the rows behind XboxStepArgs, with
-// PolySolveArgs' strides. The state bounds are read only by the XBOX instantiations (null otherwise).
+// GenSolveArgs' strides. The state bounds are read only by the XBOX instantiations (null otherwise).
 template <typename real>
 struct RowsStepArgs : XboxStepArgs<real> {
     const real *G, *h;   // G: [m][n] (sb_g = st_g = 0), [T][m][n] (0, m n) or [B][T][m][n] (T m n, m n); h likewise without [n]

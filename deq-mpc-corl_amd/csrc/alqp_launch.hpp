@@ -19,12 +19,6 @@ inline int flags_of(const T &) { return 0; }
 template <typename real>
 inline int flags_of(const SolveArgs<real> &a) { return a.flags; }
 template <typename real>
-inline int flags_of(const DenseSolveArgs<real> &a) { return a.flags; }
-template <typename real>
-inline int flags_of(const XboxSolveArgs<real> &a) { return a.flags; }
-template <typename real>
-inline int flags_of(const PolySolveArgs<real> &a) { return a.flags; }
-template <typename real>
 inline int flags_of(const ShdynSolveArgs<real> &a) { return a.flags; }
 template <typename real>
 inline int flags_of(const GenSolveArgs<real> &a) { return a.flags; }
@@ -70,21 +64,15 @@ int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream);
 template <typename real, bool DYN>
 int dispatch_backward(int nx, int nu, const BwdArgs<real, DYN> &a, hipStream_t stream);
 template <typename real>
-int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
-template <typename real>
-int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
-template <typename real>
-int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream);   // the state-bound unit
+int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream);   // the state-bound step unit
 template <typename real>
 int dispatch_step_rows(int nx, int nu, const RowsStepArgs<real> &a, hipStream_t stream);   // the row-step unit; XBOX iff a.xlo
 // the dense-step units, one object per POLY (alqp_team_dense_step, alqp_team_dense_step_rows); XBOX iff a.xlo
 template <typename real, bool POLY>
 int dispatch_step_dense(int nx, int nu, const DenseStepArgs<real> &a, hipStream_t stream);
 template <typename real>
-int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
-template <typename real>
 int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);
-// MASK: kGenDense | kGenXbox | kGenPoly, two or three of them; one object per mask (alqp_team_gen_*, -DALQP_GEN_UNIT=<mask>)
+// MASK: kGenDense | kGenXbox | kGenPoly, at least one of them; one object per mask (alqp_team_gen_*, -DALQP_GEN_UNIT=<mask>)
 constexpr int kGenDense = 1, kGenXbox = 2, kGenPoly = 4;
 template <typename real, int MASK>
 int dispatch_solve_gen(int nx, int nu, const GenSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream);

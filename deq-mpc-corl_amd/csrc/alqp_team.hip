@@ -1,7 +1,7 @@
 // alqp_team.hip - the team kernels (one QP per lane team, factor in LDS: alqp_team.hpp) and their launchers, fp32
 // and fp64 in one object.
-#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_DENSE_UNIT) || defined(ALQP_XBOX_UNIT) || defined(ALQP_POLY_UNIT) || \
-    defined(ALQP_SHDYN_UNIT) || defined(ALQP_GEN_UNIT) || defined(ALQP_ROWS_STEP_UNIT) || defined(ALQP_DENSE_STEP_UNIT)
+#if defined(ALQP_BWD_DYN_UNIT) || defined(ALQP_XBOX_STEP_UNIT) || defined(ALQP_SHDYN_UNIT) || defined(ALQP_GEN_UNIT) || \
+    defined(ALQP_ROWS_STEP_UNIT) || defined(ALQP_DENSE_STEP_UNIT)
 #undef ALQP_PHASE_TIMING   // the debug counters live in the product unit only
 #endif
 #include <hip/hip_runtime.h>
@@ -16,53 +16,35 @@ namespace alqp {
 __device__ unsigned long long g_team_cycles[8];   // debug build only (tools/team_timing.py)
 #endif
 // ---- fused LinDx solve -------------------------------------------------------------
+// One body under three headers, each in compile units of its own (build.sh):
+//   k_solve_lin (the product unit): the plain problem, SolveArgs.
+//   k_solve_lin_shdyn (-DALQP_SHDYN_UNIT): the plain problem with F and c addressed through an instance stride and a stage
+//     stride (a.sb_F / a.mt_F, a.sb_c / a.mt_c; ALQP_F_STAGE / ALQP_C_STAGE in Team), so that one F, or one sequence F_t,
+//     serves the whole batch. Same arithmetic in the same order on the same values as k_solve_lin.
+//   k_solve_lin_gen<.., DENSE, XBOX, POLY, ..> (-DALQP_GEN_UNIT=<mask>, mask = 1 dense | 2 state bounds | 4 general rows, one
+//     object per non-zero mask): every feature's arguments in one GenSolveArgs, an instantiation reads those of its flags.
+//     DENSE: the stage cost's full C_t at a.C, [B][T][N][N], in place of a.Qd. XBOX: state box rows xlo <= x_t <= xhi behind
+//     every stage's control rows, the bounds at a.xlo / a.xhi. POLY: a.m rows G_t z_t <= h_t behind those, rows and right-hand
+//     sides at a.G / a.h; the LDS image is then the team image plus a hand-over region of 2 pad4(a.m) words per team.
+//     Multipliers per stage [u | x | G] (Team).
+// Headers, not a shared device function: called through one, every plain instantiation came out with different register
+// allocation. The plain and the shdyn header stay apart from the gen one so that the hot path's argument blocks and code
+// stay what they are.
 // OCC: wavefronts per SIMD the register allocation is capped for. 2 (256 registers) lets a CU hold the 8 teams its
 // LDS has room for, but costs 80 B (fp32) / 252 B (fp64) of scratch per lane at (13,4); 1 (no cap) has no scratch.
 // Measured (profiles/r02/experiments): fp64 is faster uncapped at every batch the team kernels see (B = 200: 1.27 ->
 // 1.22 ms, B = 2048: 3.43 -> 2.85 ms); fp32 only while there is at most one wavefront per SIMD anyway (B = 200: 0.84 ->
-// 0.80 ms, B = 1024: 0.91 -> 0.87 ms; B = 2048: 1.07 against 1.71 ms). dispatch_solve() picks accordingly.
+// 0.80 ms, B = 1024: 0.91 -> 0.87 ms; B = 2048: 1.07 against 1.71 ms). dispatch_solve() picks accordingly, and
+// dispatch_solve_shdyn() by the same rule. The gen kernels have uncapped builds only: a capped one spills.
 // The TRACE instantiations (tests only) are never capped: with their extra live pointers the capped fp64 builds spill ~70-150
 // registers, and this hipcc (ROCm 7.2) can place such a spill store at the head of a divergent loop's exit block IN FRONT OF the
 // `s_or_b64 exec` that re-enables the lanes - the store then runs with EXEC = 0 and the reload returns stale scratch. Seen once
 // (k_solve_lin<double,12,4,true,2>: the zs base offset spilled after the `for (e = li; e < T*N; e += G)` load loop, every row
-// of the returned z one repeated value); the uncapped builds have no spills (checked per kernel: tools/spill_report.py).
-// The dense-cost unit (-DALQP_DENSE_UNIT) compiles this same body as k_solve_lin_dense: the stage cost's full C_t at a.C,
-// [B][T][N][N], in place of a.Qd; uncapped builds only. Two headers over one body, rather than a shared device function:
-// called through one, every plain instantiation came out with different register allocation.
-// The state-bound unit (-DALQP_XBOX_UNIT) is made the same way, a third header: k_solve_lin_xbox, state box rows
-// xlo <= x_t <= xhi behind every stage's control rows (Team's XBOX flag), the bounds at a.xlo / a.xhi; uncapped builds only.
-// That unit also holds k_newton_step_xbox, the one-step kernel below over the same Team (state bounds with a callable dx).
-// The general-row unit (-DALQP_POLY_UNIT), a fourth header: k_solve_lin_poly, a.m rows G_t z_t <= h_t behind every stage's
-// control rows (Team's POLY flag), rows and right-hand sides at a.G / a.h. Its LDS image is the team image plus a hand-over
-// region of 2 pad4(a.m) words per team. Uncapped builds only, for the reason given above: a capped build spills, and a
-// spilling build of this body is what the TRACE paragraph describes.
-// The shared-dynamics unit (-DALQP_SHDYN_UNIT), a fifth header: k_solve_lin_shdyn, the plain problem with F and c addressed
-// through an instance stride and a stage stride (a.sb_F / a.mt_F, a.sb_c / a.mt_c; ALQP_F_STAGE / ALQP_C_STAGE in Team), so
-// that one F, or one sequence F_t, serves the whole batch. Same arithmetic in the same order on the same values as
-// k_solve_lin; capped and uncapped builds chosen by the plain kernel's rule (dispatch_solve_shdyn).
-// The combination units (-DALQP_GEN_UNIT=<mask>, mask = 1 dense | 2 state bounds | 4 general rows, one object per mask with
-// two or three bits set), a sixth header: k_solve_lin_gen, the three flags as template parameters and every feature's
-// arguments in one GenSolveArgs. Multipliers per stage [u | x | G] (Team), LDS image that of the flags it has. Uncapped
-// builds only, and no spilling instantiation (tools/spill_report.py), for the reason given above.
-// The row-step unit (-DALQP_ROWS_STEP_UNIT) holds no fused solve: k_newton_step_rows below, the one-step kernel over
-// Team<.., XBOX, POLY> (general rows, with or without state bounds, with a callable dx). Uncapped builds only.
-// The dense-step units (-DALQP_DENSE_STEP_UNIT=<0|1>, the value is POLY; one object each) hold no fused solve either:
-// k_newton_step_dense below, the one-step kernel over Team<.., true, XBOX, POLY> (a full C_t with a callable dx).
+// of the returned z one repeated value); the uncapped builds have no spills (checked per kernel: tools/spill_report.py), and
+// no instantiation of this body may ship with one.
 #if defined(ALQP_GEN_UNIT)
 template <typename real, int NX, int NU, bool DENSE, bool XBOX, bool POLY, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_lin_gen(GenSolveArgs<real> a, TraceArgs<real> tr) {
-#elif defined(ALQP_DENSE_UNIT)
-template <typename real, int NX, int NU, bool TRACE>
-__global__ __launch_bounds__(64, 1) void k_solve_lin_dense(DenseSolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = true, XBOX = false, POLY = false;
-#elif defined(ALQP_XBOX_UNIT)
-template <typename real, int NX, int NU, bool TRACE>
-__global__ __launch_bounds__(64, 1) void k_solve_lin_xbox(XboxSolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = false, XBOX = true, POLY = false;
-#elif defined(ALQP_POLY_UNIT)
-template <typename real, int NX, int NU, bool TRACE>
-__global__ __launch_bounds__(64, 1) void k_solve_lin_poly(PolySolveArgs<real> a, TraceArgs<real> tr) {
-    constexpr bool DENSE = false, XBOX = false, POLY = true;
 #elif defined(ALQP_SHDYN_UNIT)
 template <typename real, int NX, int NU, bool TRACE, int OCC = TRACE ? 1 : 2>
 __global__ __launch_bounds__(64, OCC) void k_solve_lin_shdyn(ShdynSolveArgs<real> a, TraceArgs<real> tr) {
@@ -81,16 +63,10 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     const int b_raw = blockIdx.x * C::QPW + team;
     const bool active = b_raw < a.B;
     const int b = active ? b_raw : a.B - 1;
-#if defined(ALQP_GEN_UNIT)
-    const int T = a.T, M = C::M(T) + (XBOX ? 2 * T * NX : 0) + (POLY ? T * a.m : 0), neq = T * NX;
-    const int team_words = C::team_words(T) + (POLY ? 2 * pad4(a.m) : 0);   // the team image, then the hand-over region
-#elif defined(ALQP_POLY_UNIT)
-    const int T = a.T, M = C::M(T) + T * a.m, neq = T * NX;
-    const int team_words = C::team_words(T) + 2 * pad4(a.m);   // the team image, then the hand-over region
-#else
-    const int T = a.T, M = C::M(T) + (XBOX ? 2 * T * NX : 0), neq = T * NX;
-    const int team_words = C::team_words(T);
-#endif
+    int m = 0;
+    if constexpr (POLY) m = a.m;
+    const int T = a.T, M = C::M(T) + (XBOX ? 2 * T * NX : 0) + (POLY ? T * m : 0), neq = T * NX;
+    const int team_words = C::team_words(T) + (POLY ? 2 * pad4(m) : 0);   // the team image, then the hand-over region
 
     Team<real, NX, NU, DENSE, XBOX, POLY> tm;
 #ifdef ALQP_PHASE_TIMING
@@ -98,14 +74,8 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.stamp(-1);
 #endif
     tm.init(smem + (size_t)team * team_words + opaque_zero(), li, team * G, T, b);
-#if defined(ALQP_GEN_UNIT)
-    if constexpr (DENSE) tm.gC = a.C + (size_t)b * T * N * N;
+    if constexpr (DENSE) tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
     else tm.gQd = a.Qd + (size_t)b * T * N;
-#elif defined(ALQP_DENSE_UNIT)
-    tm.gC = a.C + (size_t)b * T * N * N;   // size_t: B T n n words pass 2^32 bytes at large batches
-#else
-    tm.gQd = a.Qd + (size_t)b * T * N;
-#endif
     tm.gq = a.q + (size_t)b * T * N;
 #ifdef ALQP_SHDYN_UNIT
     tm.gF = a.F + (size_t)b * a.sb_F;
@@ -119,7 +89,6 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
     tm.gulo = a.ulo + (size_t)b * a.sb_u;
     tm.guhi = a.uhi + (size_t)b * a.sb_u;
     tm.st_u = a.st_u;
-#ifdef ALQP_GEN_UNIT
     if constexpr (XBOX) {
         tm.gxlo = a.xlo + (size_t)b * a.sb_x;
         tm.gxhi = a.xhi + (size_t)b * a.sb_x;
@@ -131,18 +100,6 @@ __global__ __launch_bounds__(64, OCC) void k_solve_lin(SolveArgs<real> a, TraceA
         tm.st_g = a.st_g; tm.st_h = a.st_h; tm.pm = a.m;
         tm.ps = tm.Xp + pad4(T * C::XT);
     }
-#endif
-#ifdef ALQP_XBOX_UNIT
-    tm.gxlo = a.xlo + (size_t)b * a.sb_x;
-    tm.gxhi = a.xhi + (size_t)b * a.sb_x;
-    tm.st_x = a.st_x;
-#endif
-#ifdef ALQP_POLY_UNIT
-    tm.gG = a.G + (size_t)b * a.sb_g;
-    tm.gh = a.h + (size_t)b * a.sb_h;
-    tm.st_g = a.st_g; tm.st_h = a.st_h; tm.pm = a.m;
-    tm.ps = tm.Xp + pad4(T * C::XT);
-#endif
 
     real *gz = a.z + (size_t)b * T * N;
     tm.lams = a.lam + (size_t)b * M;  // multipliers stay in global memory (L2), updated in place
@@ -334,17 +291,17 @@ __global__ __launch_bounds__(64) void k_newton_step(StepArgs<real> a) {
     }
 }
 
-#if defined(ALQP_XBOX_UNIT) || defined(ALQP_ROWS_STEP_UNIT) || defined(ALQP_DENSE_STEP_UNIT)
+#if defined(ALQP_XBOX_STEP_UNIT) || defined(ALQP_ROWS_STEP_UNIT) || defined(ALQP_DENSE_STEP_UNIT)
 // The same with more rows per stage and / or a dense stage cost: k_newton_step's statements over Team<.., DENSE, XBOX, POLY>.
 // Three kernels, each in a unit of its own, and like the fused solve above three headers over one body (a shared device
 // function does not keep their register allocation either: profiles/r18/README.md). The members only some of the argument
 // types have (Qd, C, G, h, m) are touched inside `if constexpr`.
 // XBOX: state box rows, the bounds at gxlo / gxhi. POLY: general rows G_t z_t <= h_t, and the LDS image is the team image plus
-// the hand-over region of 2 pad4(m) words per team, set up as k_solve_lin_poly sets it up. DENSE: stage cost
+// the hand-over region of 2 pad4(m) words per team, set up as k_solve_lin_gen sets it up. DENSE: stage cost
 // 1/2 z_t' C_t z_t + q_t' z_t with C at a.C ([B][T][N][N]) and no gQd. Multipliers per stage [u | (x) | (G)],
 // M = T nx + T (2 nu + (XBOX ? 2 nx : 0) + (POLY ? m : 0)) per instance. No obstacle rows and no state-estimator row set:
 // forward_sweep's obstacle offset is written without XR.
-#if defined(ALQP_XBOX_UNIT)   // the state-bound unit: state box rows
+#if defined(ALQP_XBOX_STEP_UNIT)   // the state-bound step unit: state box rows
 template <typename real, int NX, int NU>
 __global__ __launch_bounds__(64) void k_newton_step_xbox(XboxStepArgs<real> a) {
     constexpr bool DENSE = false, XBOX = true, POLY = false;
@@ -486,7 +443,7 @@ size_t lds_bytes_for(int T) {
 }
 
 // Launches `fn` with one wavefront per workgroup and the team LDS image as dynamic LDS.
-// `extra_words`: LDS words per team behind the team image (k_solve_lin_poly's hand-over region).
+// `extra_words`: LDS words per team behind the team image (the hand-over region of the kernels with general rows).
 template <typename real, int NX, int NU, typename Fn, typename... Args>
 int launch_team_kernel_extra(Fn fn, int B, int T, int extra_words, hipStream_t stream, Args... args) {
     using C = Cfg<real, NX, NU>;
@@ -558,7 +515,14 @@ int dispatch_solve_shdyn(int nx, int nu, const ShdynSolveArgs<real> &a, const Tr
         return launch_team_kernel<real, NX, NU>(k_solve_lin_shdyn<real, NX, NU, false, 1>, a.B, a.T, stream, a, TraceArgs<real>{});
     });
 }
-#elif !defined(ALQP_DENSE_UNIT) && !defined(ALQP_XBOX_UNIT) && !defined(ALQP_POLY_UNIT)
+#elif defined(ALQP_XBOX_STEP_UNIT)
+template <typename real>
+int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream) {
+    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
+        return launch_team_kernel<real, NX, NU>(k_newton_step_xbox<real, NX, NU>, a.B, a.T, stream, a);
+    });
+}
+#else
 template <typename real>
 int dispatch_solve(int nx, int nu, const SolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
     return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
@@ -578,39 +542,6 @@ int dispatch_step(int nx, int nu, const StepArgs<real> &a, hipStream_t stream) {
         return launch_team_kernel<real, NX, NU>(k_newton_step<real, NX, NU>, a.B, a.T, stream, a);
     });
 }
-
-#elif defined(ALQP_DENSE_UNIT)
-template <typename real>
-int dispatch_solve_dense(int nx, int nu, const DenseSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
-    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
-        if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
-        return launch_team_kernel<real, NX, NU>(k_solve_lin_dense<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
-    });
-}
-#elif defined(ALQP_POLY_UNIT)
-template <typename real>
-int dispatch_solve_poly(int nx, int nu, const PolySolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
-    const int extra = 2 * pad4(a.m);
-    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
-        if (tr) return launch_team_kernel_extra<real, NX, NU>(k_solve_lin_poly<real, NX, NU, true>, a.B, a.T, extra, stream, a, *tr);
-        return launch_team_kernel_extra<real, NX, NU>(k_solve_lin_poly<real, NX, NU, false>, a.B, a.T, extra, stream, a, TraceArgs<real>{});
-    });
-}
-#else
-template <typename real>
-int dispatch_solve_xbox(int nx, int nu, const XboxSolveArgs<real> &a, const TraceArgs<real> *tr, hipStream_t stream) {
-    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
-        if (tr) return launch_team_kernel<real, NX, NU>(k_solve_lin_xbox<real, NX, NU, true>, a.B, a.T, stream, a, *tr);
-        return launch_team_kernel<real, NX, NU>(k_solve_lin_xbox<real, NX, NU, false>, a.B, a.T, stream, a, TraceArgs<real>{});
-    });
-}
-
-template <typename real>
-int dispatch_step_xbox(int nx, int nu, const XboxStepArgs<real> &a, hipStream_t stream) {
-    return for_dims(nx, nu, ALQP_E_UNSUPPORTED, [&](auto NX, auto NU) {
-        return launch_team_kernel<real, NX, NU>(k_newton_step_xbox<real, NX, NU>, a.B, a.T, stream, a);
-    });
-}
 #endif
 
 template <typename real, bool DYN>
@@ -627,10 +558,9 @@ size_t lds_query(int nx, int nu, int T) {
 
 // The DYN instantiations of k_backward are a compile unit of their own (-DALQP_BWD_DYN_UNIT, build.sh): the unit every
 // other team kernel comes out of then holds exactly the instantiations it held before they existed.
-// So are the dense-cost instantiations of the fused solve (-DALQP_DENSE_UNIT), the state-bound ones (-DALQP_XBOX_UNIT) and
-// the general-row ones (-DALQP_POLY_UNIT) and the shared-dynamics ones (-DALQP_SHDYN_UNIT), and each combination of flags
-// (-DALQP_GEN_UNIT=<mask>), and the one-step kernels with general rows (-DALQP_ROWS_STEP_UNIT) and with a dense cost
-// (-DALQP_DENSE_STEP_UNIT=<POLY>).
+// So are the shared-dynamics instantiations of the fused solve (-DALQP_SHDYN_UNIT) and each set of its feature flags
+// (-DALQP_GEN_UNIT=<mask>), and the one-step kernels with state bounds (-DALQP_XBOX_STEP_UNIT), with general rows
+// (-DALQP_ROWS_STEP_UNIT) and with a dense cost (-DALQP_DENSE_STEP_UNIT=<POLY>).
 #if defined(ALQP_GEN_UNIT)
 template int dispatch_solve_gen<float, ALQP_GEN_UNIT>(int, int, const GenSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_gen<double, ALQP_GEN_UNIT>(int, int, const GenSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
@@ -643,17 +573,9 @@ template int dispatch_step_dense<double, ALQP_DENSE_STEP_UNIT != 0>(int, int, co
 #elif defined(ALQP_SHDYN_UNIT)
 template int dispatch_solve_shdyn<float>(int, int, const ShdynSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve_shdyn<double>(int, int, const ShdynSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
-#elif defined(ALQP_POLY_UNIT)
-template int dispatch_solve_poly<float>(int, int, const PolySolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
-template int dispatch_solve_poly<double>(int, int, const PolySolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
-#elif defined(ALQP_XBOX_UNIT)
-template int dispatch_solve_xbox<float>(int, int, const XboxSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
-template int dispatch_solve_xbox<double>(int, int, const XboxSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
+#elif defined(ALQP_XBOX_STEP_UNIT)
 template int dispatch_step_xbox<float>(int, int, const XboxStepArgs<float> &, hipStream_t);
 template int dispatch_step_xbox<double>(int, int, const XboxStepArgs<double> &, hipStream_t);
-#elif defined(ALQP_DENSE_UNIT)
-template int dispatch_solve_dense<float>(int, int, const DenseSolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
-template int dispatch_solve_dense<double>(int, int, const DenseSolveArgs<double> &, const TraceArgs<double> *, hipStream_t);
 #elif !defined(ALQP_BWD_DYN_UNIT)
 template int dispatch_solve<float>(int, int, const SolveArgs<float> &, const TraceArgs<float> *, hipStream_t);
 template int dispatch_solve<double>(int, int, const SolveArgs<double> &, const TraceArgs<double> *, hipStream_t);

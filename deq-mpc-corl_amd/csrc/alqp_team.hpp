@@ -196,15 +196,15 @@ __device__ inline void wave_sync() { asm volatile("" ::: "memory"); }
 
 // ---- the team -------------------------------------------------------------------
 
-// DENSE (k_solve_lin_dense only): the stage cost is 1/2 z_t' C_t z_t + q_t' z_t with a full symmetric C_t read from gC
+// DENSE (k_solve_lin_gen<DENSE>): the stage cost is 1/2 z_t' C_t z_t + q_t' z_t with a full symmetric C_t read from gC
 // ([T][N][N] row-major, this instance) instead of diag(gQd). H lane hi keeps row hi of C_t in registers, fetched a stage
 // ahead like F; the LDS image is the same. Every DENSE statement sits behind `if constexpr`, so the DENSE = false
 // instantiations compile to the code they had before the flag existed.
-// XBOX (k_solve_lin_xbox only): state box rows xlo[t] <= x_t <= xhi[t] on every stage, behind the stage's control rows:
+// XBOX (k_solve_lin_gen<XBOX>): state box rows xlo[t] <= x_t <= xhi[t] on every stage, behind the stage's control rows:
 // per stage [u - uhi | -u + ulo | x - xhi | -x + xlo], stage stride 2 NU + 2 NX. A state row is +-e_i' like a control
 // row, so H lanes hi < NX add its penalty terms to g and D next to their equality-row terms, and the three T*NU loops
 // below get a T*NX twin. No LDS of its own. Every XBOX statement sits behind `if constexpr`.
-// POLY (k_solve_lin_poly only): pm >= 1 general rows G_t z_t <= h_t per stage, z_t = [x_t; u_t], behind the stage's control
+// POLY (k_solve_lin_gen<POLY>): pm >= 1 general rows G_t z_t <= h_t per stage, z_t = [x_t; u_t], behind the stage's control
 // rows: per stage [u - uhi | -u + ulo | G_t z_t - h_t], stage stride 2 NU + pm (pm is a run-time number). Row k of stage t,
 // r = G_k z_t - h_k, adds G_k' (lam_k + rho max(r, 0)) to g_t and rho [r >= 0] G_k' G_k to ALL of H_tt. Per stage the team
 // computes the pm residuals once (lane li takes rows li, li + G, ...; the first trip's row, h and multiplier are fetched a

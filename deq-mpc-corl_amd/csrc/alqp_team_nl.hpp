@@ -231,7 +231,7 @@ __device__ __forceinline__ void nl_merit_candidates(TM &tm, real h, real (&phi)[
 }
 
 // ---- the fused nonlinear solve with rows: k_solve_lin's statements around the three functions above -----------------
-// One team of Cfg::G lanes per instance; LDS image that of k_solve_lin_xbox / _poly / _gen. Uncapped builds only and no
+// One team of Cfg::G lanes per instance; LDS image that of k_solve_lin_gen with the same flags. Uncapped builds only and no
 // spilling instantiation (tools/spill_report.py), for the reason alqp_team.hip's header comment gives.
 template <typename real, class Dyn, bool XBOX, bool POLY, bool TRACE>
 __global__ __launch_bounds__(64, 1) void k_solve_nonlin_team(NlRowsSolveArgs<real> a, TraceArgs<real> tr) {

@@ -22,10 +22,11 @@ alqp_aux         alqp_aux.hip
 alqp_quad_f32    alqp_quad.hip        -DALQP_QUAD_F32
 alqp_quad_f64    alqp_quad.hip        -DALQP_QUAD_F64
 alqp_team_dyn      alqp_team.hip      -DALQP_BWD_DYN_UNIT
-alqp_team_dense    alqp_team.hip      -DALQP_DENSE_UNIT
-alqp_team_xbox     alqp_team.hip      -DALQP_XBOX_UNIT
-alqp_team_poly     alqp_team.hip      -DALQP_POLY_UNIT
+alqp_team_xbox_step  alqp_team.hip    -DALQP_XBOX_STEP_UNIT
 alqp_team_shdyn    alqp_team.hip      -DALQP_SHDYN_UNIT
+alqp_team_gen_d    alqp_team.hip      -DALQP_GEN_UNIT=1
+alqp_team_gen_x    alqp_team.hip      -DALQP_GEN_UNIT=2
+alqp_team_gen_p    alqp_team.hip      -DALQP_GEN_UNIT=4
 alqp_team_gen_dx   alqp_team.hip      -DALQP_GEN_UNIT=3
 alqp_team_gen_dp   alqp_team.hip      -DALQP_GEN_UNIT=5
 alqp_team_gen_xp   alqp_team.hip      -DALQP_GEN_UNIT=6

@@ -1,4 +1,4 @@
-"""GPU tests of the dense-cost fused solve (k_solve_lin_dense behind alqp_solve_lin_dense_*, MPC(diag_cost=False)).
+"""GPU tests of the dense-cost fused solve (k_solve_lin_gen<DENSE> behind alqp_solve_lin_dense_*, MPC(diag_cost=False)).
 The reference is tests/dense_cost_reference.py's backend (pinned on the CPU by tests/test_dense_cost_cpu.py), fed the
 kernel's own inputs, in the kernel's dtype. Tolerances are those tests/test_gpu_parity.py applies to the plain team
 kernel for the same quantities (RT, and 1e-10 / 2e-9 on z / lam of a full fp64 solve)."""

@@ -1,4 +1,4 @@
-"""GPU tests of the fused solve with general rows G_t z_t <= h_t (k_solve_lin_poly behind alqp_solve_lin_poly_*,
+"""GPU tests of the fused solve with general rows G_t z_t <= h_t (k_solve_lin_gen<POLY> behind alqp_solve_lin_poly_*,
 MPC(ineqG=, ineqh=)). The reference is tests/poly_rows_reference.py's backend (pinned on the CPU by
 tests/test_poly_rows_cpu.py), fed the kernel's own inputs, in the kernel's dtype. Structure and tolerances are
 tests/test_gpu_state_bounds.py's: RT, PHI_EPS, G_FLOOR and scale_err of tests/test_gpu_dense_cost.py, 1e-10 / 2e-9 on z / lam

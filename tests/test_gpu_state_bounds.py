@@ -1,4 +1,4 @@
-"""GPU tests of the state-bound fused solve (k_solve_lin_xbox behind alqp_solve_lin_xbox_*, MPC(x_lower=, x_upper=)).
+"""GPU tests of the state-bound fused solve (k_solve_lin_gen<XBOX> behind alqp_solve_lin_xbox_*, MPC(x_lower=, x_upper=)).
 The reference is tests/state_bounds_reference.py's backend (pinned on the CPU by tests/test_state_bounds_cpu.py), fed the
 kernel's own inputs, in the kernel's dtype. Tolerances and the rule for comparing fp64 line-search decisions are
 tests/test_gpu_dense_cost.py's (RT, PHI_EPS, G_FLOOR; 1e-10 / 2e-9 on z / lam of a full fp64 solve)."""

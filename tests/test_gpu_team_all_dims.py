@@ -1,5 +1,5 @@
 """GPU tests of the team solves at EVERY (nx, nu) of alqp_dims.hpp: the product builds of the dense-cost, state-bound and
-general-row kernels (k_solve_lin_dense / _xbox / _poly), the shared-dynamics kernels (k_solve_lin_shdyn and its quad
+general-row kernels (k_solve_lin_gen with one flag), the shared-dynamics kernels (k_solve_lin_shdyn and its quad
 twin; product and TRACE builds), and the register-capped fp32 builds <float, NX, NU, false, 2> of k_solve_lin and
 k_solve_lin_shdyn, which the dispatch rule launches only once the batch has more than one wavefront per SIMD.
 
