@@ -164,7 +164,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             }
             qd.forward(tg, alpha_pend, pend, (phi_from_forward && st == 0) ? &phi_prev : nullptr);
             real ph[20];
-            qd.template backward<FUSE_LS>(ph);
+            // s_t is read again only by a merit pass of its own, by the in-kernel exit's iter_end() after every step and
+            // by the iter_end() behind the last step
+            const bool store_s = !FUSE_LS || ref_exit || st + 1 == a.max_newton;
+            qd.template backward<FUSE_LS>(ph, nullptr, store_s);
             QSTAMP(-1);
             if constexpr (TRACE) {
                 if (tr.d && active) {

@@ -387,6 +387,30 @@ struct Quad {
             for (int m = H; m < L; ++m) v[m] = p[m - H];
         }
     }
+    // own slots L0 <= m < S of a field of S slots per lane into v[m]; v[m] for m < L0 is left alone. A head chunk that
+    // holds slot L0 and slots in front of it is read whole (one 16-byte access) and only its slots >= L0 are taken.
+    template <int S, int L0>
+    __device__ __forceinline__ void ld_slots_from(FRef<real> f, real (&v)[S]) const {
+        static_assert(L0 >= 0 && L0 <= S, "slots of the field");
+#pragma unroll
+        for (int c = L0 / 4; c < S / 4; ++c) {
+            const real *p = f.p + C::w(f.f.h + 16 * c) + 4 * q;
+            if (4 * c >= L0) gld4(p, v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
+            else {
+                real w[4];
+                gld4(p, w[0], w[1], w[2], w[3]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (4 * c + i >= L0) v[4 * c + i] = w[i];
+            }
+        }
+        constexpr int H = 4 * (S / 4);
+        if constexpr (S > H) {
+            const real *p = f.p + C::w(f.f.t) + 4 * q;
+#pragma unroll
+            for (int m = (L0 > H ? L0 : H); m < S; ++m) v[m] = p[m - H];
+        }
+    }
     template <int S>
     __device__ __forceinline__ void st_slots(FRef<real> f, const real (&v)[S]) const {
 #pragma unroll
@@ -495,7 +519,11 @@ struct Quad {
 
     // F_t rows of this lane: row 4s+q (zeros for rows >= NX). Loads are unconditional (row
     // index clamped, result masked) so that all of a stage's loads go out in one batch:
-    // a load inside a divergent branch cannot be hoisted and costs its own round trip.
+    // a load inside a divergent branch cannot be hoisted and costs its own round trip. That holds for a wave-uniform
+    // branch too: the sweeps load F_{T-2} once more at the last stage, which has no dynamics rows, and discard it.
+    // With the call under `dyn` hipcc splits the stage's loads into batches that wait for each other and spends ~100
+    // more VALU instructions per stage on addresses (fp32 (13,4): +1.3 % launch time, 8 B more scratch in the
+    // backward sweep; profiles/r22/README.md).
     __device__ __forceinline__ void load_F_rows(int t, WT &W) const {
         const real *Fg = gF + ALQP_F_STAGE(t);
 #pragma unroll
@@ -767,6 +795,10 @@ struct Quad {
         // carried from stage to stage, own rows / elements only (row 4s+q of block t-1 pins element 4s+q of x_t):
         // vpo = lam + rho r of the previous row block, Syo = (W y) of the previous stage
         real vpo[SW], Syo[SW];
+        // own x-slots (m < SW) of z_t, pending step applied: stage t-1 needs them for its residual and hands them on,
+        // so a stage reads only the slots m >= SW of its own z (and d) from the record. Not with EXT: the caller's
+        // arrays are read element-wise and their x part is not a slot range of the n-vector.
+        real zc[SW];
 #pragma unroll
         for (int i = 0; i < ST; ++i) S[i] = 0;
 #pragma unroll
@@ -797,6 +829,7 @@ struct Quad {
                 if constexpr (C::PHI0_FWD) mdist += valid ? fma_(fma_(real(0.5) * rho, r, li[s]), r, real(0)) : real(0);  // initial-state rows
                 Syo[s] = 0;
                 r0[s] = r;
+                zc[s] = z0[s];
             }
             if (!EXT && active) st_own_x(recp(T - 1) + C::oR, r0);
         }
@@ -836,7 +869,9 @@ struct Quad {
                     bu = has ? guhi[t * st_u + jc] : real(0);
                     bl = has ? gulo[t * st_u + jc] : real(0);
                 } else {
-                    ld_own_n(rp + C::oZ, zs);
+#pragma unroll
+                    for (int s = 0; s < SW; ++s) zs[s] = zc[s];
+                    ld_slots_from<SY, SW>(rp + C::oZ, zs);
                     if constexpr (ALQP_EXP_NOQ) { for (int m = 0; m < SY; ++m) Qo[m] = real(1); }
                     else ld_own_n(rp + C::oQ, Qo);
                     ld_own_n(rp + C::oq, qo);
@@ -848,13 +883,16 @@ struct Quad {
                 }
                 if (pending) {  // wave-uniform: z_t += alpha d_t, z_{t+1}[x] += alpha d_{t+1}[x]
                     real dt[SY], dn[SW];
-                    ld_own_n(rp + C::oY, dt);
+                    constexpr int M0 = EXT ? 0 : SW;   // the slots in front came advanced from the previous stage (zc)
+                    ld_slots_from<SY, M0>(rp + C::oY, dt);
                     ld_ownx_of_n(rn + C::oY, dn);
 #pragma unroll
-                    for (int m = 0; m < SY; ++m) zs[m] = fma_(alpha, dt[m], zs[m]);   // written back with the stage results
+                    for (int m = M0; m < SY; ++m) zs[m] = fma_(alpha, dt[m], zs[m]);   // written back with the stage results
 #pragma unroll
                     for (int s = 0; s < SW; ++s) zn[s] = fma_(alpha, dn[s], zn[s]);
                 }
+#pragma unroll
+                for (int s = 0; s < SW; ++s) zc[s] = zn[s];   // the next stage's zs[m < SW]: the same words, the same fma
                 ALQP_STAMP(0);  // forward: exposed load latency
 #pragma unroll
                 for (int k = 0; k < N; ++k) zt[k] = qbv(zs[k >> 2], k);
@@ -1191,8 +1229,11 @@ struct Quad {
     // stages in sweep order T-1..0). The extra inputs sit in the record next to L and y.
     // d_ext (one Newton direction for the caller, k_newton_step_quad): d goes straight to the caller's array and
     // s = (J d)_eq, which only the fused line search reads, is not stored
+    // store_s = false: s stays in registers, where the fused line search takes it from. Only iter_end() and
+    // merit_candidates() read the record's s group, so a Newton step that another forward sweep follows need not
+    // write it; k_backward_quad forms its s from F and w and does not rely on the group either.
     template <bool LS>
-    __device__ __forceinline__ void backward(real (&phi)[20], real *d_ext = nullptr) {
+    __device__ __forceinline__ void backward(real (&phi)[20], real *d_ext = nullptr, bool store_s = true) {
         constexpr int MU0 = NX / 4;  // first element slot that can hold a control
         real c0 = 0, c1 = 0, c2 = 0;
         real acc[20];
@@ -1275,7 +1316,7 @@ struct Quad {
                     for (int k = 0; k < N; ++k) p = fma_(W[s][k], Y[k], p);
                     sv[s] = (4 * s + 3 < NX || r < NX) ? dxs[s] - p : real(0);
                 }
-                if (!ALQP_EXP_NORS && active && !d_ext) st_own_x(rp + C::oS, sv);
+                if (!ALQP_EXP_NORS && active && !d_ext && store_s) st_own_x(rp + C::oS, sv);
             }
             if constexpr (LS) {
                 real zu = 0, du = 0;   // the control this lane owns (at most one: NU <= 4)
@@ -1329,7 +1370,7 @@ struct Quad {
             ALQP_STAMP(5);  // backward: solves + stores
         }
         // initial-state rows: s = d_0[x]
-        if (active && !d_ext) st_own_x(recp(T - 1) + C::oS, dxs);
+        if (active && !d_ext && store_s) st_own_x(recp(T - 1) + C::oS, dxs);
         if constexpr (LS) {
 #pragma unroll
             for (int s = 0; s < SW; ++s) {
