@@ -61,6 +61,7 @@ ALQP_DUAL_UPDATE = 2
 ALQP_SAVE_FACTOR = 4
 ALQP_WS_PRIMED = 8
 ALQP_EXIT_IN_KERNEL = 16
+ALQP_FACTOR_IN_WS = 32
 ALQP_E_COOP = -4
 VARIANT_AUTO, VARIANT_TEAM, VARIANT_QUAD = 0, 1, 2
 

@@ -86,6 +86,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     Quad<real, NX, NU> qd;
     __shared__ real w_lds[QCfg<real, NX, NU>::WLDS_WORDS];   // fp64: the W panel (WPanel); one word otherwise
     qd.wl = w_lds + threadIdx.x;
+    // fp32: the factor of the first stages stays in LDS between the sweeps (QCfg::KL, Quad::fchunk)
+    constexpr bool FL = C::KL > 0;
+    if constexpr (FL) {
+        __shared__ __attribute__((aligned(16))) real l_lds[C::KL * C::FLW];
+        qd.fl = (ALQP_LDS real *)l_lds;
+        qd.kl = (a.flags & ALQP_FACTOR_IN_WS) ? 0 : (T < C::KL ? T : C::KL);
+    }
     qd.q = lane & 3;
     qd.T = T;
     qd.active = active;
@@ -162,12 +169,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 qd.template linearize<Dyn>(alpha_pend, pend);
                 pend = false;
             }
-            qd.forward(tg, alpha_pend, pend, (phi_from_forward && st == 0) ? &phi_prev : nullptr);
+            // the records a launch leaves behind hold the factor of its last Newton step at every stage
+            // (k_backward_quad reads it there): that step's sweep stores the LDS-held stages to the records too. With
+            // the in-kernel exit any step can be the last.
+            if constexpr (FL) qd.fl_ws = ref_exit || (it + 1 == a.al_iter && st + 1 == a.max_newton);
+            qd.template forward<false, FL>(tg, alpha_pend, pend, (phi_from_forward && st == 0) ? &phi_prev : nullptr);
             real ph[20];
             // s_t is read again only by a merit pass of its own, by the in-kernel exit's iter_end() after every step and
             // by the iter_end() behind the last step
             const bool store_s = !FUSE_LS || ref_exit || st + 1 == a.max_newton;
-            qd.template backward<FUSE_LS>(ph, nullptr, store_s);
+            qd.template backward<FUSE_LS, FL>(ph, nullptr, store_s);
             QSTAMP(-1);
             if constexpr (TRACE) {
                 if (tr.d && active) {

@@ -112,6 +112,21 @@ __device__ inline void gst4(double *p, double a, double b, double c, double d) {
     d4u t; t.x = a; t.y = b; t.z = c; t.w = d;
     *reinterpret_cast<d4u *>(p) = t;
 }
+// ---- 16-byte-aligned access to LDS (fp32: one ds_read_b128 / ds_write_b128). The pointers carry the address space:
+// a generic pointer that is LDS in one branch and global memory in the other becomes flat accesses word by word.
+#define ALQP_LDS __attribute__((address_space(3)))
+template <typename real>
+__device__ inline void lld4(const ALQP_LDS real *p, real &a, real &b, real &c, real &d) {
+    typedef real v4 __attribute__((ext_vector_type(4)));
+    const v4 t = *(const ALQP_LDS v4 *)p;
+    a = t.x; b = t.y; c = t.z; d = t.w;
+}
+template <typename real>
+__device__ inline void lst4(ALQP_LDS real *p, real a, real b, real c, real d) {
+    typedef real v4 __attribute__((ext_vector_type(4)));
+    v4 t; t.x = a; t.y = b; t.z = c; t.w = d;
+    *(ALQP_LDS v4 *)p = t;
+}
 // LEN contiguous reals into a register array (static indices only)
 template <int LEN, typename real>
 __device__ inline void gload(const real *p, real (&dst)[LEN]) {
@@ -240,6 +255,32 @@ struct QCfg {
 #endif
     static constexpr bool W_LDS = ALQP_W_LDS && (sizeof(real) == 8 || ALQP_W_LDS_F32);   // the W rows live in LDS (WPanel)
     static constexpr int WLDS_WORDS = W_LDS ? SW * N * 64 : 1;          // reals of LDS per wavefront
+    // ---- the factor of the first KL stages in LDS (fp32, fused solve only: Quad::forward / backward with FL). Between
+    // the forward and the backward sweep's visit of stage t the chip moves (T - 1 - t) stages' worth of records, so
+    // the factors of the first stages are the ones that go out to HBM and come back; the wavefront's LDS (one
+    // wavefront per SIMD: a quarter of the CU's 160 KB) is otherwise unused in fp32. One chunk (slot s, c) of a
+    // wavefront's 16 instances is lane-contiguous, 16 bytes per lane that owns a row: 64 lanes in a full slot,
+    // 16 * NLAST in the last one (quad-major, the quad's owning lanes side by side).
+    __host__ __device__ static constexpr int fl_chunk(int s) { return 16 * 4 * lanes_of(s); }   // words of one chunk of slot s
+    __host__ __device__ static constexpr int fl_base(int s) {                                   // word offset of slot s
+        int o = 0;
+        for (int i = 0; i < s; ++i) o += (i + 1) * fl_chunk(i);
+        return o;
+    }
+    static constexpr int FLW = fl_base(SH);            // words of one stage's factor, 16 instances
+    static constexpr int FL_BUDGET = 36 * 1024 / 4;    // words per wavefront: leaves the CU's four wavefronts resident
+    // stages held: as many whole stages as fit, at most 8 (a short horizon then crosses the boundary at every size);
+    // -DALQP_FACTOR_LDS_F32=k sets it, 0 gives the kernel without any of this
+#ifndef ALQP_FACTOR_LDS_F32
+#define ALQP_FACTOR_LDS_F32 -1
+#endif
+    // n = 18 (14,4) keeps every stage in the records: with the LDS stores in its forward sweep hipcc spills 156 B per
+    // lane there (8 B without; two stages would fit)
+    static constexpr int KL = (sizeof(real) != 4 || W_LDS) ? 0
+                              : ALQP_FACTOR_LDS_F32 >= 0   ? ALQP_FACTOR_LDS_F32
+                              : N > 17                     ? 0
+                              : (FL_BUDGET / FLW < 8 ? FL_BUDGET / FLW : 8);
+    static_assert(KL * FLW <= 40 * 1024 / 4, "four wavefronts' factor stages fit a CU's LDS");
     __host__ __device__ static constexpr int p4(int x) { return (x + 3) & ~3; }
     // The record also carries the stage's slice of every small per-stage array (working copies
     // of z and lam, copies of diag Q, q, c and the bounds): in their own arrays these are 52-68
@@ -346,6 +387,69 @@ struct Quad {
     int nobs;
     real obs_r2;
     bool no_init;
+    // fused solve, fp32 (QCfg::KL > 0; forward / backward with FL): the factor of the stages t < kl lives in the
+    // wavefront's LDS, which starts at fl (one wavefront per block: lane = thread). kl = min(KL, T), or 0 under
+    // ALQP_FACTOR_IN_WS; fl_ws: this forward sweep also stores those stages to the records (the launch's last Newton
+    // step: the records a launch leaves behind hold every stage's factor)
+    ALQP_LDS real *fl;
+    int kl;
+    bool fl_ws;
+    // this stage's words of this lane (full chunks) and of this quad (last-slot chunks). The lane number is taken
+    // afresh at every stage (two instructions, kept in the loop by `volatile`): an address register that lives through
+    // the panel phase costs spills there (the kernel runs at 256 + 256 registers)
+    __device__ __forceinline__ void fstage(int t, ALQP_LDS real *&pl, ALQP_LDS real *&pc) const {
+        int lane;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+        pl = fl + t * C::FLW + 4 * lane;
+        pc = fl + t * C::FLW + 4 * C::NLAST * (lane >> 2);
+    }
+    __device__ __forceinline__ ALQP_LDS real *fchunk(ALQP_LDS real *pl, ALQP_LDS real *pc, int s, int c, int ql) const {
+        return (C::lanes_of(s) == 4 ? pl : pc + 4 * ql) + C::fl_base(s) + c * C::fl_chunk(s);
+    }
+    // the factor chunks of a stage between registers (H, trimmed panel) and the record / LDS
+    __device__ __forceinline__ void st_factor_ws(real *rp, const real (&H)[HT]) const {
+#pragma unroll
+        for (int s = 0; s < SH; ++s)
+#pragma unroll
+            for (int c = 0; c <= s; ++c)
+                if (C::lanes_of(s) == 4 || q < C::lanes_of(s))
+                    gst4(lchunk(rp, s, c, q), H[C::hidx(s, 4 * c)],
+                         H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
+    }
+    __device__ __forceinline__ void st_factor_lds(int t, const real (&H)[HT]) const {
+        ALQP_LDS real *pl, *pc;
+        fstage(t, pl, pc);
+#pragma unroll
+        for (int s = 0; s < SH; ++s)
+#pragma unroll
+            for (int c = 0; c <= s; ++c)
+                if (C::lanes_of(s) == 4 || q < C::lanes_of(s))
+                    lst4<real>(fchunk(pl, pc, s, c, q), H[C::hidx(s, 4 * c)],
+                         H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
+    }
+    // lanes without a real row re-read lane 0's words (unconditional load, values unused)
+    __device__ __forceinline__ void ld_factor_ws(real *rp, real (&H)[HT]) const {
+#pragma unroll
+        for (int s = 0; s < SH; ++s)
+#pragma unroll
+            for (int c = 0; c <= s; ++c) {
+                const int ql = (C::lanes_of(s) == 4 || q < C::lanes_of(s)) ? q : 0;
+                gld4(lchunk(rp, s, c, ql), H[C::hidx(s, 4 * c)],
+                     H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
+            }
+    }
+    __device__ __forceinline__ void ld_factor_lds(int t, real (&H)[HT]) const {
+        ALQP_LDS real *pl, *pc;
+        fstage(t, pl, pc);
+#pragma unroll
+        for (int s = 0; s < SH; ++s)
+#pragma unroll
+            for (int c = 0; c <= s; ++c) {
+                const int ql = (C::lanes_of(s) == 4 || q < C::lanes_of(s)) ? q : 0;
+                lld4<real>(fchunk(pl, pc, s, c, ql), H[C::hidx(s, 4 * c)],
+                     H[C::hidx(s, 4 * c + 1)], H[C::hidx(s, 4 * c + 2)], H[C::hidx(s, 4 * c + 3)]);
+            }
+    }
 
     __device__ __forceinline__ real uhi(int t, int j) const { return guhi[t * st_u + j]; }
     __device__ __forceinline__ real ulo(int t, int j) const { return gulo[t * st_u + j]; }
@@ -788,7 +892,9 @@ struct Quad {
     // stage's vectors come straight from the caller's arrays (own elements, one word per instruction) and the
     // residual is z_{t+1}[x] - xnext_t with the caller's xnext = f(z_t) (gxn); nothing but the factor and y is
     // written. Saves the copy-in pass, the pass that formed c_t = xnext - F z (a third read of F) and the re-read.
-    template <bool EXT = false>
+    // FL (fused solve, QCfg::KL > 0): the factor of the stages t < kl goes to LDS (fchunk), and to the record as well
+    // only under fl_ws
+    template <bool EXT = false, bool FL = false>
     __device__ __forceinline__ void forward(real *g_out, real alpha, bool pending, real *phi0, const real *gxn = nullptr) {
         real mdist = 0;  // merit terms, per-lane parts (own elements and rows; summed over the quad at the end)
         real S[ST], Sy[SW];
@@ -1123,6 +1229,9 @@ struct Quad {
             ALQP_STAMP(2);  // forward: panel
             // ---- stage results -> workspace (each lane its own words)
             if (active) {
+                if constexpr (FL) {
+                    if (t >= kl || fl_ws) st_factor_ws(rp, H);   // wave-uniform
+                } else
                 if (!(ALQP_EXP_NOL && t >= T - ALQP_EXP_NOL))
 #pragma unroll
                 for (int s = 0; s < SH; ++s)
@@ -1135,6 +1244,12 @@ struct Quad {
                 own_of<N, SY>(Y, yo);
                 st_own_n(rp + C::oY, yo);
                 if (pending) st_own_n(rp + C::oZ, zs);
+            }
+            if constexpr (FL) {
+                // wave-uniform. Padding quads too: their backward sweep reads what they wrote, as it reads instance
+                // B - 1's records. Behind the stores to the record: in front of them hipcc spills in the F'F phase
+                // (16 B of scratch per lane, the launch 1 % slower than without any of this; profiles/r23/README.md)
+                if (t < kl) st_factor_lds(t, H);
             }
 
             if constexpr (C::S_AFTER) {
@@ -1232,7 +1347,8 @@ struct Quad {
     // store_s = false: s stays in registers, where the fused line search takes it from. Only iter_end() and
     // merit_candidates() read the record's s group, so a Newton step that another forward sweep follows need not
     // write it; k_backward_quad forms its s from F and w and does not rely on the group either.
-    template <bool LS>
+    // FL: the factor of the stages t < kl is read from LDS, where this launch's forward<.., FL> left it
+    template <bool LS, bool FL = false>
     __device__ __forceinline__ void backward(real (&phi)[20], real *d_ext = nullptr, bool store_s = true) {
         constexpr int MU0 = NX / 4;  // first element slot that can hold a control
         real c0 = 0, c1 = 0, c2 = 0;
@@ -1249,6 +1365,11 @@ struct Quad {
             const bool dyn = t < T - 1;
             real *rp = recp(t);
             real H[HT];
+            if constexpr (FL) {
+                static_assert(!FL || !ALQP_EXP_NOL, "the no-factor experiment runs with the factor in the records");
+                if (t < kl) ld_factor_lds(t, H);   // wave-uniform
+                else ld_factor_ws(rp, H);
+            } else
             if (ALQP_EXP_NOL && t >= T - ALQP_EXP_NOL) {
 #pragma unroll
                 for (int i = 0; i < HT; ++i) H[i] = real(1);

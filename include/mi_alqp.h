@@ -74,6 +74,10 @@ typedef struct AlqpObstacles {
                                skip_flag. Returns ALQP_E_COOP when the grid cannot be co-resident (the caller then uses
                                the launch-per-step route). Single-GPU batches only: a batch sharded over ranks needs the
                                all-reduce between the steps. */
+#define ALQP_FACTOR_IN_WS 32 /* quad variant, fp32: the fused solve keeps the factor of every stage in the workspace records
+                               between its two sweeps, none in LDS (csrc/alqp_quad.hpp, QCfg::KL). Results and the workspace
+                               left behind are the same bits either way; for tests and A/B timing. Ignored elsewhere.
+                               (Bits 20-31: wavefront stagger experiments.) */
 
 typedef struct AlqpParams {
     int al_iter;      /* AL outer iterations done by this call (AL_mpc.py:290) */
