@@ -255,6 +255,15 @@ struct QCfg {
 #endif
     static constexpr bool W_LDS = ALQP_W_LDS && (sizeof(real) == 8 || ALQP_W_LDS_F32);   // the W rows live in LDS (WPanel)
     static constexpr int WLDS_WORDS = W_LDS ? SW * N * 64 : 1;          // reals of LDS per wavefront
+    // the panel's multipliers are scaled by -1/p_j on the lane that owns the row, before the quad broadcast
+    // (Quad::forward); -DALQP_PANEL_OWNER_SCALE=0 compiles the broadcast-then-multiply source (A/B builds)
+#ifndef ALQP_PANEL_OWNER_SCALE
+#define ALQP_PANEL_OWNER_SCALE 1
+#endif
+#ifndef ALQP_PANEL_OWNER_SCALE_F64
+#define ALQP_PANEL_OWNER_SCALE_F64 ALQP_PANEL_OWNER_SCALE
+#endif
+    static constexpr bool OWNER_SCALE = sizeof(real) == 8 ? ALQP_PANEL_OWNER_SCALE_F64 : ALQP_PANEL_OWNER_SCALE;
     // ---- the factor of the first KL stages in LDS (fp32, fused solve only: Quad::forward / backward with FL). Between
     // the forward and the backward sweep's visit of stage t the chip moves (T - 1 - t) stages' worth of records, so
     // the factors of the first stages are the ones that go out to HBM and come back; the wavefront's LDS (one
@@ -881,6 +890,20 @@ struct Quad {
         for (int k = 0; k < 20; ++k) phi[k] = qbv(m[k >> 2], k);
     }
 
+    // The panel's multiplier of row k at pivot j and the sign of the column operand that goes with it. OWNER_SCALE:
+    // hs holds column j scaled by -1/p_j on the lanes that own its rows, the broadcast carries -l_kj and the updates
+    // are fma(a, -l_kj, c). Otherwise l_kj = Hh[k][j] * (1/p_j) is formed behind the broadcast, on all four lanes,
+    // and the updates are fma(-a, l_kj, c). The same operands reach every multiply and fma either way.
+    template <int NHS>
+    __device__ __forceinline__ static real panel_mult(const real (&H)[HT], const real (&hs)[NHS], real ip, int j, int k) {
+        if constexpr (C::OWNER_SCALE) return qbv(hs[k >> 2], k);
+        else return qbv(H[C::hidx(k >> 2, j)], k) * ip;
+    }
+    __device__ __forceinline__ static real pcol(real a) {
+        if constexpr (C::OWNER_SCALE) return a;
+        else return -a;
+    }
+
     // ---- forward sweep: gradient, factorisation, forward substitution ------------------
     // With `pending`, the step alpha*d the previous line search chose (d is still in the
     // records) is applied on the fly: z_t is read, advanced, used and written back here, which
@@ -1170,6 +1193,18 @@ struct Quad {
                 // and the step stays a descent direction for the line search to judge; the reference's
                 // half-finished cholesky_ex factor (al_utils.py:510-515) has nothing to restate
                 const real ip = rcp_(fabs_(p));
+                // The multiplier l_kj = Hh[k][j] / p_j, negated, is formed by the owner of row k BEFORE the quad
+                // broadcast: 1/p_j is the same on every lane, so one multiply per slot of the column replaces one per
+                // row k on all four lanes, and the broadcast carries the same 32 (64) bits the multiply behind it used
+                // to make. Scaling by -1/p_j turns fma(-a, l, c) into fma(a, -l, c): the same product, the same
+                // rounding, no sign flip to spend an instruction on. Words of hs above the diagonal and on row-less
+                // lanes of the last slot are never the source lane of a broadcast and are not read otherwise.
+                real hs[C::OWNER_SCALE ? SH : 1];
+                if constexpr (C::OWNER_SCALE) {
+                    const real nip = -ip;
+#pragma unroll
+                    for (int m = (j >> 2); m < SH; ++m) hs[m] = H[C::hidx(m, j)] * nip;
+                }
                 if constexpr (C::W_LDS) {
                     // W lives in LDS (fp64): its columns are read KB at a time, ALL reads of a group first, then the
                     // updates, then the writes. Element by element (read, 2-3 instructions, use, write - what hipcc makes
@@ -1192,31 +1227,38 @@ struct Quad {
                         for (int kk = 0; kk < KB; ++kk) {
                             const int k = k0 + kk;
                             if (k < N) {
-                                const real lkj = qbv(H[C::hidx(k >> 2, j)], k) * ip;
+                                const real lkj = panel_mult(H, hs, ip, j, k);
 #pragma unroll
-                                for (int s = (k >> 2); s < SH; ++s) H[C::hidx(s, k)] = fma_(-H[C::hidx(s, j)], lkj, H[C::hidx(s, k)]);
+                                for (int s = (k >> 2); s < SH; ++s) H[C::hidx(s, k)] = fma_(pcol(H[C::hidx(s, j)]), lkj, H[C::hidx(s, k)]);
 #pragma unroll
-                                for (int s = 0; s < SW; ++s) W[s][k] = fma_(-wj[s], lkj, wv[kk][s]);
-                                Y[k] = fma_(-Y[j], lkj, Y[k]);
+                                for (int s = 0; s < SW; ++s) W[s][k] = fma_(pcol(wj[s]), lkj, wv[kk][s]);
+                                Y[k] = fma_(pcol(Y[j]), lkj, Y[k]);
                             }
                         }
                     }
                 } else {
 #pragma unroll
                 for (int k = j + 1; k < N; ++k) {
-                    const real lkj = qbv(H[C::hidx(k >> 2, j)], k) * ip;
+                    const real lkj = panel_mult(H, hs, ip, j, k);
 #pragma unroll
-                    for (int s = (k >> 2); s < SH; ++s) H[C::hidx(s, k)] = fma_(-H[C::hidx(s, j)], lkj, H[C::hidx(s, k)]);
+                    for (int s = (k >> 2); s < SH; ++s) H[C::hidx(s, k)] = fma_(pcol(H[C::hidx(s, j)]), lkj, H[C::hidx(s, k)]);
 #pragma unroll
-                    for (int s = 0; s < SW; ++s) W[s][k] = fma_(-W[s][j], lkj, W[s][k]);
-                    Y[k] = fma_(-Y[j], lkj, Y[k]);
+                    for (int s = 0; s < SW; ++s) W[s][k] = fma_(pcol(W[s][j]), lkj, W[s][k]);
+                    Y[k] = fma_(pcol(Y[j]), lkj, Y[k]);
                 }
                 }
                 if constexpr (C::S_AFTER) ipv[j] = ip;
                 if (!C::S_AFTER && dyn) {
+                    real wsc[C::OWNER_SCALE ? SW : 1];   // W[b][j] / p_j on the owner of row b, as hs above
+                    if constexpr (C::OWNER_SCALE) {
+#pragma unroll
+                        for (int s = 0; s < SW; ++s) wsc[s] = W[s][j] * ip;
+                    }
 #pragma unroll
                     for (int b = 0; b < NX; ++b) {
-                        const real wbj = qbv(W[b >> 2][j], b) * ip;
+                        real wbj;
+                        if constexpr (C::OWNER_SCALE) wbj = qbv(wsc[b >> 2], b);
+                        else wbj = qbv(W[b >> 2][j], b) * ip;
 #pragma unroll
                         for (int s = (b >> 2); s < SW; ++s) S[C::hidx(s, b)] = fma_(W[s][j], wbj, S[C::hidx(s, b)]);
                     }
@@ -1257,9 +1299,16 @@ struct Quad {
                 if (dyn) {
 #pragma unroll
                     for (int j = 0; j < N; ++j) {
+                        real wsc[C::OWNER_SCALE ? SW : 1];
+                        if constexpr (C::OWNER_SCALE) {
+#pragma unroll
+                            for (int s = 0; s < SW; ++s) wsc[s] = W[s][j] * ipv[j];
+                        }
 #pragma unroll
                         for (int b = 0; b < NX; ++b) {
-                            const real wbj = qbv(W[b >> 2][j], b) * ipv[j];
+                            real wbj;
+                            if constexpr (C::OWNER_SCALE) wbj = qbv(wsc[b >> 2], b);
+                            else wbj = qbv(W[b >> 2][j], b) * ipv[j];
 #pragma unroll
                             for (int s = (b >> 2); s < SW; ++s) S[C::hidx(s, b)] = fma_(W[s][j], wbj, S[C::hidx(s, b)]);
                         }
