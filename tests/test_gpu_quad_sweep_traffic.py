@@ -49,10 +49,19 @@ grid17 = pytest.mark.parametrize("nx,nu,T,dtype", [(nx, nu, T, dt) for (nx, nu) 
                                                    for dt in ("f32", "f64")])
 
 
+# (nx, nu, T, B) -> seed of the cases that are not drawn with SEED. Empty for every case of this file and of
+# test_gpu_quad_factor_lds.py; test_gpu_quad_all_dims.py enters its two (chosen from the oracle's trace on the CPU,
+# test_quad_all_dims_cases_cpu.py), so that _reference here and _run / _oracle there draw the same problem for them.
+CASE_SEEDS = {}
+
+
 @functools.lru_cache(maxsize=None)
-def _problem_cpu(nx, nu, T, B, dtype):
+def _problem_cpu(nx, nu, T, B, dtype, seed=None):
+    """seed = None: the case's seed, SEED unless CASE_SEEDS names another"""
     from deq_mpc_corl_amd import synthetic_problem
-    return synthetic_problem(B, T, nx, nu, seed=SEED, dtype=TD[dtype])
+    if seed is None:
+        seed = CASE_SEEDS.get((nx, nu, T, B), SEED)
+    return synthetic_problem(B, T, nx, nu, seed=seed, dtype=TD[dtype])
 
 
 def _state(p, B, T, nx, nu, dt, dev):
